@@ -2,6 +2,17 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c5|...] [--spp S]
                     [--scaling strong|weak] [--schedule cost|tiles] [--consolidate auto|on|off]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`, the workload).  Everything else -- the counting passes and `roofline`, the
+streaming-read probe, `cpu_baseline`, and for N > 1 the timing of the other scaling mode -- runs
+only with `--full` (where the `--no-*` options still switch single legs off).
+
+--dump-outputs DIR writes the framebuffer of the last timed step (what a caller of the timed path
+receives: rgb sums + pass count per pixel) as DIR/framebuffer.npy, float32 [H, W, 4]; a frame of
+more than 64 MB is written as a fixed seeded sample of its pixels, [n, 4].  The scene, camera and
+seed are fixed by the arguments, so two builds can be compared output for output.
 
 One step = one full render of the configured workload (all `spp` SamplePixel passes for
 every pixel of the image; each pass continues the pixel's XORWOW stream, exactly like the
@@ -23,7 +34,7 @@ reported as a side field (`weak_scaling` / `strong_scaling`).
 Denoising + Mix + BGRA8 to the host, path_tracer.cu:256-306) with one and with several row-tile
 contexts, and prints a separate JSON line (not the headline metric).
 
-Rank 0 prints one JSON line with `roofline` (SURVEY.md §8(d) algorithmic bytes ÷ the kernel's
+Rank 0 prints one JSON line; with --full it holds `roofline` (SURVEY.md §8(d) algorithmic bytes ÷ the kernel's
 HIP-event time, beside the rocprof-measured HBM bytes and VALU issue of a committed profile of
 the same workload) and `cpu_baseline` (the scalar oracle on a bounded sample of the same
 workload on the host cores, 1 thread and all usable cores).
@@ -91,6 +102,12 @@ def parse_args(argv=None):
     ap.add_argument("--dispatch-schedule", default="previous", choices=["previous", "tiles"],
                     help="--dispatch: the per-pass render's tile order (previous: heaviest first by the last pass's "
                          "draws, as PathTracer::DispatchRay does; tiles: row-major)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: counting passes + roofline, the streaming-read "
+                         "probe, the CPU baseline, and for N > 1 the other scaling mode")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's framebuffer to DIR/framebuffer.npy (float32; a seeded pixel "
+                         "sample when the frame exceeds 64 MB)")
     ap.add_argument("--profile-json", default=None,
                     help="rocprof summary of this workload (profiles/rocprof_*.json, tools/rocprof_summary.py)")
     return ap.parse_args(argv)
@@ -203,6 +220,25 @@ def load_profile(path, config, n_rows, spp, gpu_path, walk, schedule):
         pj = json.load(f)
     want = {"config": config, "n_rows": n_rows, "spp": spp, "path": gpu_path, "walk": walk, "schedule": schedule}
     return pj if all(pj.get(k) == v for k, v in want.items()) else None
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: the most one run writes
+DUMP_SAMPLE_SEED = 1234   # fixed: two runs with the same arguments sample the same pixels
+
+
+def dump_outputs(out_dir, fb):
+    """Write the framebuffer `fb` (float32 [H, W, 4]) as out_dir/framebuffer.npy.  A frame above
+    DUMP_MAX_BYTES is written as [n, 4]: the pixels (row-major indices into H*W) of a fixed seeded
+    sample drawn without replacement, in ascending order."""
+    import numpy as np
+    fb = np.ascontiguousarray(fb, dtype=np.float32)
+    if fb.nbytes > DUMP_MAX_BYTES:
+        px = fb.reshape(-1, fb.shape[-1])
+        n = DUMP_MAX_BYTES // (px.shape[1] * 4)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], size=n, replace=False))
+        fb = np.ascontiguousarray(px[idx])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "framebuffer.npy"), fb)
 
 
 # ---------------------------------------------------------------------------------------
@@ -340,7 +376,7 @@ def run(args):
         return dict(zip(KEYS + ("global_nodes",), (int(x) for x in v.tolist())))
 
     walk_info = r.walk_info()
-    hbm_ceiling = r.measure_read_bandwidth(4 << 30, 10) if not args.no_hbm_probe else None
+    hbm_ceiling = r.measure_read_bandwidth(4 << 30, 10) if args.full and not args.no_hbm_probe else None
     wide = ordered and walk_info["n_wide"] > 0
     # Global-memory bytes per node visit of the executed walk: the wide walk reads the top
     # LDS_TREE_NODES nodes from the workgroup's LDS image (loaded once per workgroup per launch,
@@ -350,7 +386,7 @@ def run(args):
     n_lds = min(walk_info["n_wide"], LDS_TREE_NODES)
     walk_node_bytes = 0 if lds_image else 32
     st = walk_counts = walk_diff = None
-    if not args.no_count:
+    if args.full and not args.no_count:
         st = count_pass(False)
         walk_counts = st
         if ordered:
@@ -375,8 +411,9 @@ def run(args):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    fb_last = None
     for _ in range(args.steps):
-        step(timed=True)
+        fb_last = step(timed=True)
     torch.cuda.synchronize()
     if use_pg:
         dist.barrier()
@@ -390,12 +427,19 @@ def run(args):
         t = _all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, avg_kernel_ms_max = t.tolist()
 
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # the last timed step's frame: the stitched framebuffer every rank holds after the gather,
+        # or without a process group the context's own accumulator (all H rows)
+        fb = fb_last.cpu().numpy() if fb_last is not None else r.read_accum()
+        dump_outputs(args.dump_outputs, fb.reshape(H, W, 4))
+    del fb_last
+
     # N > 1: the other scaling mode over the same ranks, 1 untimed + 2 timed frames with the
     # gather -- strong (the default): the weak-scaled frame (pixels per GPU fixed); weak: the
     # configuration's own frame strong-scaled (the north star's 1920x1080 at N GPUs, whose
     # ceiling is the longest pixel chain).
     other = None
-    if world > 1 and not args.no_strong_check:
+    if world > 1 and args.full and not args.no_strong_check:
         if args.scaling == "weak":
             Wx, Hx, mode = W0, H0, "strong"
         else:
@@ -545,7 +589,7 @@ def run(args):
                 roof["limiter"] = prof["limiter"]
                 roof["profile"] = prof["source"]
             out["roofline"] = roof
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, objs, sky, cam, seconds_hint=args.cpu_seconds)
             except Exception as e:  # the baseline must never sink the GPU measurement

@@ -284,8 +284,12 @@ int cpt_set_frame(cpt_ctx* c, int width, int height, const int32_t* rows, int n_
         HIP_TRY(c, hipMemcpy(c->d_rows, r.data(), r.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMalloc((void**)&c->d_rng, 6 * npix * sizeof(uint32_t)));
         HIP_TRY(c, hipMalloc((void**)&c->d_accum, npix * sizeof(float4)));
-        HIP_TRY(c, hipMemset(c->d_accum, 0, npix * sizeof(float4)));
-        HIP_TRY(c, hipMemset(c->d_rng, 0, 6 * npix * sizeof(uint32_t)));
+        // on the context's stream, and waited for: a device hipMemset returns before the fill has
+        // run and is ordered on the null stream only, which the context's non-blocking stream does
+        // not wait for; on a busy GPU the fill could land after cpt_init_rng's kernel or a render
+        HIP_TRY(c, hipMemsetAsync(c->d_accum, 0, npix * sizeof(float4), c->stream()));
+        HIP_TRY(c, hipMemsetAsync(c->d_rng, 0, 6 * npix * sizeof(uint32_t), c->stream()));
+        HIP_TRY(c, hipStreamSynchronize(c->stream()));
     }
     c->frame_set = true;
     c->rng_set = false;

@@ -64,3 +64,28 @@ def test_defaults_are_the_baseline_workload():
     assert (a.gpus, a.config, a.scaling, a.walk, a.path) == (None, "c4", "strong", "ordered", "megakernel")
     assert b.parse_args(["--config", "c5"]).config == "c5"
     assert a.dispatch == 0   # the per-pass DispatchRay timing is opt-in, never the default line
+    assert a.full is False and a.dump_outputs is None   # a plain run: the headline only, nothing written
+    assert b.parse_args(["--full"]).full is True
+
+
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path):
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(3)
+    small = rng.random((36, 64, 4), dtype=np.float32)
+    b.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(tmp_path / "a" / "framebuffer.npy")
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, small)
+    # one pixel row past the limit: a sample of exactly the limit, the same pixels every time
+    h = b.DUMP_MAX_BYTES // (1024 * 16) + 1
+    big = np.arange(h * 1024 * 4, dtype=np.float32).reshape(h, 1024, 4)
+    b.dump_outputs(str(tmp_path / "b"), big)
+    b.dump_outputs(str(tmp_path / "c"), big)
+    s1 = np.load(tmp_path / "b" / "framebuffer.npy")
+    s2 = np.load(tmp_path / "c" / "framebuffer.npy")
+    assert s1.dtype == np.float32 and s1.shape == (b.DUMP_MAX_BYTES // 16, 4) and s1.nbytes <= b.DUMP_MAX_BYTES
+    np.testing.assert_array_equal(s1, s2)
+    idx = (s1[:, 0] / 4).astype(np.int64)            # big's pixel p holds 4p .. 4p+3 (4p < 2^26 is exact in f32)
+    assert (np.diff(idx) > 0).all() and idx[-1] < h * 1024
+    np.testing.assert_array_equal(s1, big.reshape(-1, 4)[idx])

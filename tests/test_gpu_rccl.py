@@ -86,7 +86,7 @@ def test_bench_under_torchrun_world1():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
            "--gpus", "1", "--config", "c4", "--width", "128", "--height", "64", "--spp", "4",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-hbm-probe"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-hbm-probe"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -194,7 +194,7 @@ def test_bench_two_ranks_balanced_partition():
     the stitched frame's walk parity count is 0 and the line names the partition."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--config", "c4", "--width", "256",
            "--height", "120", "--spp", "8", "--steps", "1", "--warmup", "1", "--partition", "balanced",
-           "--no-cpu-baseline", "--no-hbm-probe", "--no-strong-check"]
+           "--full", "--no-cpu-baseline", "--no-hbm-probe", "--no-strong-check"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CPT_BENCH_BACKEND="gloo")
     r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
