@@ -353,7 +353,11 @@ __device__ __forceinline__ bool sure_f32(double d) {
     return hi - 0x38100000u < 0x07f00000u && (dm_ >= 1024 || dm_ <= -1024);
 }
 
-// pow(x, y) for a float x in [2^-126, 1] and 0 < y <= 1 with |y ln x| <= 2 (else ok = false):
+// pow(x, y) for a float x in [2^-126, 1] and 0 < y <= 1 with |y ln x| <= 23 (else ok = false;
+// ln 2^-33 = -22.9: every x_1 the lobe draws at every exponent y <= 1.  The form's relative error
+// is the absolute error of t = y ln x, which grows with |t|: ~2^-49 up to |t| = 2, so below 2^-45
+// up to 23, still inside sure_f32's 2^-43; with the bound at 2 a material of smoothness below
+// 0.35, y > 2 / 22.9, took the full sequence for part of its draws):
 // x = 2^e m, ln x = e ln2 - ln c_i + log1p(m c_i - 1) (i: m's top 7 fraction bits; the fma is
 // exact), then exp(t) = 2^(n/128) P(s) with n = round(t 128/ln2) (the 1.5 2^52 shifter: n is
 // the low word), s the remainder in units of ln2/128, 2^(n>>7) applied to T_j's exponent field.
@@ -383,7 +387,7 @@ __device__ __forceinline__ double pow_unit(float x, double y, bool& ok) {
     const double T = g_exp_tab[n & (FM_EXP_N - 1)];
     const double Ts = __hiloint2double(__double2hiint(T) + (int)((uint32_t)(n >> 7) << 20), __double2loint(T));
     const double d = Ts * p;
-    ok = ux - 0x00800000u <= 0x3f000000u && y > 0.0 && y <= 1.0 && t >= -2.0 && sure_f32(d);
+    ok = ux - 0x00800000u <= 0x3f000000u && y > 0.0 && y <= 1.0 && t >= -23.0 && sure_f32(d);
     return d;
 }
 

@@ -960,15 +960,34 @@ __device__ bool cert_case(uint64_t seed, uint64_t i, int which) {
 // which = 8: lobe_pow(x, y) vs (float)dm::pow(x, y), y = the double with the bits of `seed`;
 // 9: how many x take pow's fallback; 10: lobe_sincos(phi) vs dm::sincosf_(phi), both results;
 // 11: how many phi take sincos' fallback; 12: miss_atanf / miss_asinf vs dm::atanf_ / dm::asinf_;
-// 13: how many x take either one's fallback (asinf: x in [-1, 1]).  out[0] = count, out[1..] =
-// some of the floats' bits.
+// 13: how many x take either one's fallback (asinf: x in [-1, 1]); 17: lobe_pow vs (float)dm::pow
+// at hashed material exponents, for the indices [0, n): smoothness s = a hash of (seed, i >> 20)
+// in [0, 6], y = 1.0 / (double)dm::powf_(1000.0f, s) as k_prepare_materials forms it, x = a hash
+// of (seed, i) over the float patterns of [2^-33, 1] (the lobe's x_1 range); 18: how many of the
+// same (x, y) take pow's fallback.  out[0] = count, out[1..] = some of the floats' bits (17, 18:
+// s in the low word).
 __global__ void k_selftest_fm(int which, uint64_t n, uint64_t seed, unsigned long long* out, int out_len) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     const double y = __longlong_as_double((long long)seed);
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float x = __uint_as_float((uint32_t)i);
+        float x = __uint_as_float((uint32_t)i);
+        uint32_t low = 0u;
         bool flag;
-        if (which >= 14) {
+        if (which >= 17) {
+            const uint64_t key = seed * 0x9e3779b97f4a7c15ULL;
+            const float s = (float)(hash32(key + (i >> 20)) >> 8) * (6.0f / 16777215.0f);
+            const double ys = 1.0 / (double)dm::powf_(1000.0f, s);
+            // 0x2f000000 = 2^-33 .. 0x3f800000 = 1.0f: 0x10800001 patterns
+            x = __uint_as_float(0x2f000000u + (uint32_t)(((uint64_t)hash32(~key + i) * 0x10800001ull) >> 32));
+            low = __float_as_uint(s);
+            if (which == 17) {
+                flag = __float_as_uint(lobe_pow(x, ys)) != __float_as_uint((float)dm::pow((double)x, ys));
+            } else {
+                bool ok;
+                (void)fm::pow_unit(x, ys, ok);
+                flag = !ok && !(ys == 0.5 && x >= 0x1p-42f);
+            }
+        } else if (which >= 14) {
             flag = cert_case(seed, i, which);
         } else if (which == 8) {
             flag = __float_as_uint(lobe_pow(x, y)) != __float_as_uint((float)dm::pow((double)x, y));
@@ -998,7 +1017,7 @@ __global__ void k_selftest_fm(int which, uint64_t n, uint64_t seed, unsigned lon
         }
         if (flag) {
             unsigned long long k = atomicAdd(&out[0], 1ull);
-            if ((long long)k + 1 < out_len) out[k + 1] = ((unsigned long long)__float_as_uint(x) << 32);
+            if ((long long)k + 1 < out_len) out[k + 1] = ((unsigned long long)__float_as_uint(x) << 32) | low;
         }
     }
 }
@@ -1400,6 +1419,7 @@ __global__ void k_math_batch(int op, const float* a, const float* b, float* out,
         case 7: r = x / y; break;
         case 8: r = __builtin_sqrtf(x); break;
         case 9: r = dm::pow5f(x); break;
+        case 10: r = lobe_pow(x, 1.0 / (double)y); break;
         default: r = __builtin_nanf("");
     }
     out[i] = r;

@@ -390,7 +390,8 @@ int cpt_cap_disk_bound(float radius, float* out);
 /* Device-math known-answer surface used by the parity tests: op 0 powf(a,b), 1 sinf(a),
  * 2 cosf(a), 3 asinf(a), 4 atanf(a), 5 (float)pow((double)a, 1.0/(double)b),
  * 6 (float)((double)a / (double)b) [IEEE f64 division], 7 a / b [f32 division],
- * 8 sqrtf(a), 9 pow(a, 5) as schlick computes it (dm::pow5f). */
+ * 8 sqrtf(a), 9 pow(a, 5) as schlick computes it (dm::pow5f), 10 the BSDF lobe's short pow
+ * lobe_pow(a, 1.0/(double)b) (the same float as op 5). */
 int cpt_math_batch(cpt_ctx* ctx, int op, const float* a, const float* b, float* out, size_t n);
 /* Device self-test of the exact-quotient kernel helper against the hardware IEEE f32 divide
  * over n hashed operand pairs (which: 0 all bit patterns, 1 slab-like ranges, 2 mid ranges).
@@ -413,6 +414,11 @@ int cpt_math_batch(cpt_ctx* ctx, int op, const float* a, const float* b, float* 
  * slab test on n hashed cases from `seed` (boxes, rays, distances within 16 ulps of a plane):
  * out[0] counts the cases it certifies and the exact test rejects (0 expected); which = 15 counts
  * the certified cases and which = 16 the cases the exact test passes.
+ * which = 17: lobe_pow against (float)pow(x, y) at hashed material exponents, for the indices
+ * [0, n): smoothness s = a hash of (seed, i >> 20) in [0, 6], y = 1.0 / (double)powf(1000, s) as the
+ * material set-up forms it, x = a hash of (seed, i) over the float patterns of [2^-33, 1];
+ * which = 18: counts the same pairs whose guard sends them to the full pow (17, 18: the failing
+ * pairs are (x bits << 32 | s bits)).
  * out[0] receives the mismatch count (0 expected), out[1..out_len) up to out_len-1 failing
  * pairs as (a bits << 32 | d bits). */
 int cpt_selftest_qdiv(cpt_ctx* ctx, int which, uint64_t n, uint64_t seed, uint64_t* out, int out_len);

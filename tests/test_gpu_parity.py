@@ -134,6 +134,72 @@ def test_lobe_pow_exhaustive(gpu, oracle_mod):
         assert fell - 0x00800000 < 1e-5 * n, (y, fell)
 
 
+def _hash32(x):
+    """cpt_kernels.hip hash32 on a uint64 array."""
+    x = np.asarray(x, dtype=np.uint64)
+    x = x ^ (x >> np.uint64(33))
+    x = x * np.uint64(0xff51afd7ed558ccd)
+    x = x ^ (x >> np.uint64(33))
+    x = x * np.uint64(0xc4ceb9fe1a85ec53)
+    x = x ^ (x >> np.uint64(33))
+    return (x & np.uint64(0xffffffff)).astype(np.uint32)
+
+
+def _hashed_smoothness(n, seed):
+    """n float smoothness values in [0, 6]."""
+    h = _hash32(np.arange(n, dtype=np.uint64) + np.uint64(seed))
+    return ((h >> np.uint32(8)).astype(np.float32) * np.float32(6.0 / 16777215.0)).astype(np.float32)
+
+
+def test_lobe_pow_any_exponent(gpu):
+    """lobe_pow(x, y) == (float)dm::pow(x, y) at the exponents the API accepts, not only the demo
+    scenes': 4096 hashed smoothness values in [0, 6], y = 1.0 / (double)powf(1000, s) as
+    k_prepare_materials forms it, 2^20 hashed x over the float patterns of [2^-33, 1] for each
+    (cpt_selftest_qdiv which = 17).  The guard's fallbacks on the same pairs (which = 18): the
+    rounding guard rejects 2 * 1024 of the 2^29 low-bit patterns, about 4e-6; before pow_unit's
+    domain was widened from |y ln x| <= 2 to 23 the share was 3.7e-2 (smoothness below 0.35)."""
+    n = 1 << 32
+    cnt, pairs = gpu.selftest_qdiv(17, n, seed=20261019)
+    assert cnt == 0, [(float(x), float(s)) for x, s in pairs]
+    fell, _ = gpu.selftest_qdiv(18, n, seed=20261019)
+    print("lobe_pow fallback share over hashed exponents:", fell / n)
+    assert fell < 1e-4 * n, fell
+
+
+def test_lobe_pow_exhaustive_more_exponents(gpu, oracle_mod):
+    """test_lobe_pow_exhaustive's check, every float x in [0, 1], at 16 further exponents: the
+    smoothness values 0 .. 6 below (0: the exponent exactly 1.0), the exponent just below 1.0,
+    and four hashed smoothness values."""
+    n = int(np.float32(1.0).view(np.uint32)) + 1
+    sm = [0.0, 0.25, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 5.0, 5.999, 6.0] + [float(s) for s in _hashed_smoothness(4, 77)]
+    ys = [1.0 / float(oracle_mod.lib().or_powf(np.float32(1000.0), np.float32(s))) for s in sm]
+    ys.append(float(np.nextafter(1.0, 0.0)))
+    assert len(set(ys)) == 16 and ys[0] == 1.0
+    for y in ys:
+        cnt, xs = gpu.selftest_qdiv(8, n, seed=int(np.float64(y).view(np.uint64)))
+        assert cnt == 0, (y, [float(x) for x, _ in xs])
+
+
+def test_lobe_pow_vs_oracle(gpu, oracle_mod):
+    """The short form against the oracle directly (k_math_batch op 10 = lobe_pow(a, 1.0 /
+    (double)b) vs the oracle's op 5, (float)pow((double)a, 1.0 / (double)b)): 4096 hashed
+    smoothness values in [0, 6], b = powf(1000, s) from the device's op 0, 1024 hashed a over
+    the float patterns of [2^-33, 1] for each."""
+    ns, nx = 4096, 1024
+    s = _hashed_smoothness(ns, 4242)
+    alpha = gpu.math_batch(0, np.full(ns, 1000.0, np.float32), s)
+    np.testing.assert_array_equal(alpha.view(np.uint32),
+                                  oracle_mod.math_batch(0, np.full(ns, 1000.0, np.float32), s).view(np.uint32))
+    h = _hash32(np.arange(ns * nx, dtype=np.uint64) + np.uint64(0x5eed0000))
+    a = (np.uint32(0x2f000000) + ((h.astype(np.uint64) * np.uint64(0x10800001)) >> np.uint64(32)).astype(np.uint32))
+    a = a.view(np.float32)
+    assert a.min() >= np.float32(2.0 ** -33) and a.max() <= 1.0
+    b = np.repeat(alpha, nx)
+    g = gpu.math_batch(10, a, b)
+    o = oracle_mod.math_batch(5, a, b)
+    np.testing.assert_array_equal(g.view(np.uint32), o.view(np.uint32))
+
+
 def test_lobe_sincos_exhaustive(gpu):
     """The lobe's sinf/cosf of phi = (float)(2 pi x_2) through the short table form + rounding
     guard (cpt_device.hpp lobe_sincos) == the full dm::sincosf_ sequence, both results, for all
@@ -188,9 +254,9 @@ def test_rng_init_bitexact(gpu, oracle_mod, w, rows):
 
 # ------------------------------------------------------------------------- integrator
 def _run_both(gpu, oracle_mod, sky, objs, W, H, spp, depth, rows=None, seed=1234, aux=False, env=True,
-              path="megakernel"):
+              path="megakernel", cam=None):
     rows = np.arange(H, dtype=np.int32) if rows is None else np.asarray(rows, np.int32)
-    cam = camera_get_copy(scenes.camera_for(W, H))
+    cam = camera_get_copy(scenes.camera_for(W, H) if cam is None else cam)
     gpu.set_scene(objs)
     gpu.set_env(sky if env else None)
     gpu.set_frame(W, H, rows)
