@@ -13,6 +13,10 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libcpt.so")
 
 SOURCES = [
+    os.path.join(CSRC, "cpt_megakernel.hip"),
+    os.path.join(CSRC, "cpt_schedule.hip"),
+    os.path.join(CSRC, "cpt_display.hip"),
+    os.path.join(CSRC, "cpt_selftest.hip"),
     os.path.join(CSRC, "cpt_kernels.hip"),
     os.path.join(CSRC, "cpt_wavefront.hip"),
     os.path.join(CSRC, "cpt_capi.cpp"),
@@ -20,17 +24,6 @@ SOURCES = [
     os.path.join(CSRC, "cpt_host_bvh.cpp"),
     os.path.join(CSRC, "cpt_host_rng.cpp"),
     os.path.join(CSRC, "cpt_api.cpp"),
-]
-HEADERS = [
-    os.path.join(CSRC, "cpt_device.hpp"),
-    os.path.join(CSRC, "cpt_internal.hpp"),
-    os.path.join(CSRC, "cpt_context.hpp"),
-    os.path.join(CSRC, "cpt_host.hpp"),
-    os.path.join(CSRC, "cpt_path.hpp"),
-    os.path.join(CSRC, "cpt_stamps.hpp"),
-    os.path.join(CSRC, "cpt_tuning.hpp"),
-    os.path.join(CSRC, "cpt_dn_exp.hpp"),
-    os.path.join(REPO_DIR, "include", "cpt.h"),
 ]
 
 # Float semantics: no FMA contraction, IEEE f32 div/sqrt, no fast math,
@@ -68,19 +61,22 @@ def _hipcc():
     return "hipcc"
 
 
-def _extra_sources():
-    return [s for s in SOURCES if os.path.exists(s)]
+def build_deps():
+    """What libcpt.so is built from, as found on disk: every file under csrc/, include/cpt.h and
+    include/cpppathtracer/, and this file (the flags)."""
+    inc = os.path.join(REPO_DIR, "include")
+    deps = [os.path.join(inc, "cpt.h"), os.path.abspath(__file__)]
+    for d in (CSRC, os.path.join(inc, "cpppathtracer")):
+        for root, _, files in os.walk(d):
+            deps += [os.path.join(root, f) for f in files]
+    return [d for d in deps if os.path.exists(d)]
 
 
 def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = _extra_sources() + [h for h in HEADERS if os.path.exists(h)] + [os.path.abspath(__file__)]   # (the flags)
-    deps += [os.path.join(REPO_DIR, "include", "cpppathtracer", f)
-             for f in os.listdir(os.path.join(REPO_DIR, "include", "cpppathtracer"))] if os.path.isdir(
-        os.path.join(REPO_DIR, "include", "cpppathtracer")) else []
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in build_deps())
 
 
 def build(force: bool = False, verbose: bool = False, out: str = None, defines=()) -> str:
@@ -94,7 +90,7 @@ def build(force: bool = False, verbose: bool = False, out: str = None, defines=(
     os.makedirs(os.path.dirname(os.path.abspath(target)), exist_ok=True)
     tmp = target + ".tmp"
     cmd = [_hipcc(), *HIPCC_FLAGS, *[f"-D{d}" for d in defines], "-I", os.path.join(REPO_DIR, "include"), "-o", tmp,
-           *_extra_sources()]
+           *SOURCES]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)

@@ -472,7 +472,7 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
             HIP_TRY(c, cpt::launch_tile_schedule(p, passes, c->d_sched, c->cap_sched, c->d_tile_order, s));
             p.tile_order = c->d_tile_order;
         }
-        // Tail consolidation (cpt_kernels.hip): one slab of hand-over slots per workgroup of the
+        // Tail consolidation (cpt_megakernel.hip): one slab of hand-over slots per workgroup of the
         // persistent grid (one LDS workgroup of 1024 lanes per CU), 3 x 256 chains each.  By
         // default for frames of more than 1 and at most 4 pixels per lane and chains of at least
         // 512 passes: with more pixels the tail is a small part of the render, with short chains

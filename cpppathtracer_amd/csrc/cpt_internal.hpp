@@ -79,10 +79,11 @@ enum : uint32_t {
     CPT_DEVERR_RESUME_CAP = 4u,        // consolidation slab too small for the grid
 };
 
-// Cost schedule (cpt_kernels.hip, DESIGN.md §Cost schedule): a `passes`-pass pilot of the
+// Cost schedule (cpt_schedule.hip, DESIGN.md §Cost schedule): a `passes`-pass pilot of the
 // megakernel sums each 8x8 tile's work, then `order` (one u32 per tile) gets the tiles
 // heaviest first.  `scratch` holds tile_schedule_scratch_bytes() bytes.
 size_t tile_schedule_scratch_bytes(int width, int n_rows);
+hipError_t launch_cost_pilot(const KParams& p, hipStream_t stream);   // cpt_megakernel.hip: the pilot's launch
 // CPT_SCHEDULE_PREVIOUS: each 8x8 tile's RNG draws since `d_prev` (the Weyl plane d of the
 // states, planar [5] of p.rng), then d_prev := d; the tiles sorted heaviest first into `order`.
 hipError_t launch_tile_order_from_draws(const KParams& p, uint32_t* d_prev, void* scratch, size_t scratch_bytes,
@@ -143,6 +144,7 @@ hipError_t launch_read_pattern(int bpl, const float* p, size_t n_lanes, float* o
 hipError_t timeline_read(unsigned long long* out, int n, hipStream_t stream);
 hipError_t launch_selftest_qdiv(int which, uint64_t n, uint64_t seed, unsigned long long* out, int out_len,
                                 hipStream_t stream);
+hipError_t launch_selftest_dn_weight(int which, uint64_t n, unsigned long long* out, int out_len, hipStream_t stream);
 hipError_t launch_stitch_rows(const float4* src_acc, const float* src_nrm, const float* src_dep, const int32_t* dst_row,
                               int width, int n_rows, float4* acc, float* nrm, float* dep, hipStream_t stream);
 // out_host (nullable): the device alias of a pinned host frame, written beside `out`; accum /

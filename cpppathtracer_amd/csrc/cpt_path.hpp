@@ -1,5 +1,5 @@
 // cpt_path.hpp — device functions of the integrator shared by the megakernel
-// (cpt_kernels.hip) and the wavefront kernels (cpt_wavefront.hip): environment fetch,
+// (cpt_megakernel.hip) and the wavefront kernels (cpt_wavefront.hip): environment fetch,
 // intersectors, BVH walk, BSDF sampling, miss, camera ray generation.
 #pragma once
 

@@ -28,7 +28,7 @@ constexpr int DEFER_MISS_ROUND = 40;
 // (profiles/r02/reh_static_first_*.log; r05: C4 neutral, C2 30.2k vs 24.0k Mpaths/s without it).
 constexpr bool STATIC_FIRST = true;
 // The refill draws a tile's worth of pixel ids per counter atomic and serves the wave's idle lanes
-// from them over the following rounds (cpt_kernels.hip k_megakernel).  1-spp C4 render 1.43 vs
+// from them over the following rounds (cpt_megakernel.hip k_megakernel).  1-spp C4 render 1.43 vs
 // 2.43 ms; 128 ids 1.50 ms; requesting the next range ahead of need 1.49-1.56 ms
 // (profiles/r04/ab_take_batch_*.log); 32 / 128 ids for long chains tied / lost (r05
 // ab_take_range_long.log).  The consolidating kernel takes exactly what it needs: its ranks hold

@@ -1,5 +1,5 @@
 """Exact replacements the device code uses instead of slower IEEE sequences (cpt_device.hpp
-dm::div_pi -- also under the display's pair weights, cpt_kernels.hip dn_weight --, dm::div255; cpt_path.hpp mirror_index's division-free range).  Each must return
+dm::div_pi -- also under the display's pair weights, cpt_display.hip dn_weight --, dm::div255; cpt_path.hpp mirror_index's division-free range).  Each must return
 the bit pattern of the expression it replaces, checked here exhaustively on the host: the
 formulas are plain IEEE double operations (fma included), which the GPU executes alike."""
 import os
@@ -43,7 +43,7 @@ int main(void) {
             n++;
         }
     }
-    /* the denoise weights' range (cpt_kernels.hip dn_weight): every float in [2, 2341); from
+    /* the denoise weights' range (cpt_display.hip dn_weight): every float in [2, 2341); from
        2341 on, exp(-x / pi) is below exp's underflow bound and dn_weight returns 0 directly */
     {
         float lim = 2341.0f;
@@ -86,7 +86,7 @@ def test_exact_identities(tmp_path):
 
 # The display's pair weight against the oracle's own expression min(exp(-(double)d2 / M_PI), 1.0)
 # stored to float (oracle or_exp = dm_exp, path_tracer.cu:224,228,231), for every float d2 in
-# [0, 2341] and the special values: the round-4 branch-free form (cpt_kernels.hip dn_weight_slow:
+# [0, 2341] and the special values: the round-4 branch-free form (cpt_display.hip dn_weight_slow:
 # the quotient, dm_exp's steps with a plain ldexp below x = -105.05, the shortcuts 0 -> 1,
 # >= 330 -> 0), and the round-5 short form (dn_weight: the 2^(-j/32) table exp of
 # cpt_dn_exp.hpp and the rounding guard that falls back to the slow form).  The harness calls the
@@ -107,7 +107,7 @@ static float ref_w(float d2) {
     double w = or_exp(-((double)d2) / REF_PI);
     return (float)(w < 1.0 ? w : 1.0);
 }
-static float fast_w(float d2) {   /* cpt_kernels.hip dn_weight, operation for operation */
+static float fast_w(float d2) {   /* cpt_display.hip dn_weight, operation for operation */
     const double INV_PI = 1.0 / REF_PI;
     const double a = (double)d2, q = a * INV_PI;
     const double x = -fma(fma(-q, REF_PI, a), INV_PI, q);
@@ -125,7 +125,7 @@ static float fast_w(float d2) {   /* cpt_kernels.hip dn_weight, operation for op
 }
 static const double DN_TAB[cpt::DN_EXP_N] = CPT_DN_EXP_TABLE_INIT;
 static int g_guard_fallbacks[8];
-static float short_w(float d2, int t) {   /* cpt_kernels.hip dn_exp_short + dn_weight */
+static float short_w(float d2, int t) {   /* cpt_display.hip dn_exp_short + dn_weight */
     const double SHIFT = 0x1.8p52, a = (double)d2;
     const double tt = fma(a, cpt::DN_KN_HI, SHIFT), nd = tt - SHIFT;
     uint64_t tb; memcpy(&tb, &tt, 8);

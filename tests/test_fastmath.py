@@ -145,7 +145,7 @@ static int g_mode, g_step;
 static double g_y;
 static uint32_t g_lo, g_hi;
 static unsigned long long g_bad[8], g_fell[8], g_n[8];
-static uint32_t hash32(uint64_t x) {   /* cpt_kernels.hip hash32 */
+static uint32_t hash32(uint64_t x) {   /* cpt_selftest.hip hash32 */
     x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
     return (uint32_t)x;
 }

@@ -98,7 +98,7 @@ def test_sqrt_nn_exhaustive(gpu):
 
 
 def test_dn_weight_exhaustive(gpu):
-    """The display weight (cpt_kernels.hip dn_weight: the short table exp + rounding guard) ==
+    """The display weight (cpt_display.hip dn_weight: the short table exp + rounding guard) ==
     its slow form dn_weight_slow (the round-4 sequence, itself equal to the oracle's
     min(dm_exp(-(double)d2 / M_PI), 1.0) on every float in [0, 2341]:
     test_exact_identities.py::test_denoise_weight_exhaustive) for all 2^31 non-negative float
@@ -135,7 +135,7 @@ def test_lobe_pow_exhaustive(gpu, oracle_mod):
 
 
 def _hash32(x):
-    """cpt_kernels.hip hash32 on a uint64 array."""
+    """cpt_selftest.hip hash32 on a uint64 array."""
     x = np.asarray(x, dtype=np.uint64)
     x = x ^ (x >> np.uint64(33))
     x = x * np.uint64(0xff51afd7ed558ccd)
