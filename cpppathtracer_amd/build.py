@@ -20,6 +20,9 @@ SOURCES = [
     os.path.join(CSRC, "cpt_kernels.hip"),
     os.path.join(CSRC, "cpt_wavefront.hip"),
     os.path.join(CSRC, "cpt_capi.cpp"),
+    os.path.join(CSRC, "cpt_capi_gather.cpp"),
+    os.path.join(CSRC, "cpt_capi_display.cpp"),
+    os.path.join(CSRC, "cpt_capi_probes.cpp"),
     os.path.join(CSRC, "cpt_scene.cpp"),
     os.path.join(CSRC, "cpt_host_bvh.cpp"),
     os.path.join(CSRC, "cpt_host_rng.cpp"),

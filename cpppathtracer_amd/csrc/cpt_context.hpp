@@ -1,6 +1,8 @@
 // cpt_context.hpp — the C-ABI's context (struct cpt_ctx of include/cpt.h) and the helpers its
-// implementation files share: cpt_capi.cpp (context, frame, RNG, render, gather, display) and
-// cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  Host code only.
+// implementation files share: cpt_capi.cpp (context, frame, RNG, render, accumulator, counters),
+// cpt_capi_gather.cpp (row-tile gather), cpt_capi_display.cpp (display path), cpt_capi_probes.cpp
+// (diagnostic probes, self-tests) and cpt_scene.cpp (scene upload, material slots, walk trees,
+// device refit).  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,25 +12,64 @@
 #include <vector>
 
 #include "../../include/cpt.h"
+#include "cpt_devmem.hpp"
 #include "cpt_host.hpp"
 #include "cpt_internal.hpp"
 
 using cpt::Mat;
 using cpt::Node;
 using cpt::TexDesc;
+using cpt::ctx::DevBuf;
+using cpt::ctx::DevEvent;
 using cpt::host::HostBvh;
+
+// The wavefront path's storage, owned beside the plain view (cpt::WfState) the launchers take.
+struct WfStorage {
+    std::vector<DevBuf<uint8_t>> mem;   // 12 float4 + 4 RNG + 3 queue arrays and the counts
+    // All arrays for `npix` pixels and the view of them, or nothing: a failed allocation
+    // part-way leaves both as they were (cpt_capi.cpp, the one list of the arrays).
+    int alloc(cpt_ctx* c, size_t npix, cpt::WfState& view);
+};
+
+// Everything that lives and dies with cpt_set_frame (which assigns a fresh Frame): the device
+// buffers sized by the frame and the flags that say what they hold.
+struct Frame {
+    bool set = false, rng_set = false;
+    DevBuf<int32_t> d_rows;
+    DevBuf<uint32_t> d_rng;
+    DevBuf<float4> d_accum;
+    DevBuf<float> d_normal, d_depth;
+    // rng init (released again once the states are written)
+    DevBuf<uint32_t> d_scratch_w, d_scratch_m;
+    DevBuf<uint8_t> d_sched;     // cost schedule: pilot tile costs + sort scratch (bytes)
+    DevBuf<uint32_t> d_tile_order;
+    // CPT_SCHEDULE_PREVIOUS: the Weyl plane after the last such render, and the tile order
+    // its draws gave (the next render's dequeue order)
+    DevBuf<uint32_t> d_prev_d, d_prev_order;
+    bool prev_d_valid = false, prev_order_valid = false;
+    int prev_since_order = 0;   // renders since the CPT_SCHEDULE_PREVIOUS order was rebuilt
+    cpt::WfState wf{};           // wavefront path state (allocated on first use)
+    WfStorage wf_mem;
+    bool wf_ready = false;
+    DevBuf<float> d_mix;         // display running mean (Mix), rgb per pixel of the display band
+    DevBuf<uint8_t> d_bgra;      // display frame (band rows)
+    DevBuf<float4> d_dn_sink;    // k_denoise_strip: where lanes without an output pixel store (DN_SINK_SLOTS)
+    int band_y0 = -1, band_y1 = -1;   // display band the buffers hold
+};
 
 // ======================================================================================
 // Context
 // ======================================================================================
 struct cpt_ctx {
     int device = 0;
-    hipStream_t own_stream = nullptr;
+    int cus = 1;   // the device's compute units (read once, cpt_create)
+    // declared before the buffers and events: destroyed after them
+    cpt::ctx::DevStream own_stream;
     hipStream_t user_stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    hipEvent_t ev_main = nullptr;   // after the cost schedule's pilot: the dominant kernel(s) only
+    DevEvent ev_start, ev_stop;
+    DevEvent ev_main;   // after the cost schedule's pilot: the dominant kernel(s) only
     bool have_timing = false;
-    hipEvent_t ev_dn0 = nullptr, ev_dn1 = nullptr;   // around the last display kernel (k_denoise_rows)
+    DevEvent ev_dn0, ev_dn1;   // around the last display kernel (k_denoise_rows)
     bool have_dn_timing = false;
     std::string err;
 
@@ -46,9 +87,8 @@ struct cpt_ctx {
     std::vector<int> mat_have_tex;     // per material slot: textured?
     std::vector<uint64_t> mat_tex;     // per material slot: texture handle (textured slots)
     std::vector<int> mat_of_obj;       // object index -> material index
-    Node* d_nodes = nullptr;
-    Mat* d_mats = nullptr;
-    size_t cap_nodes = 0, cap_mats = 0;
+    DevBuf<Node> d_nodes;
+    DevBuf<Mat> d_mats;
     bool scene_set = false;
     // device refit (cpt_update_objects): the plan of both trees (ids: reference tree, then walk
     // tree), parents, heights, each object's walk-tree leaf, the boxes as built
@@ -57,59 +97,31 @@ struct cpt_ctx {
     std::vector<cpt::Box6> refit_boxes;
     std::vector<uint8_t> refit_mark;   // scratch of an update batch (all zero between batches)
     int refit_n_ref = 0;
-    cpt::RefitNode* d_refit_plan = nullptr;
-    cpt::Box6* d_refit_boxes = nullptr;
-    uint8_t* d_refit_work = nullptr;   // an update batch: RefitLeaf records, then the dirty node ids
-    size_t cap_refit_plan = 0, cap_refit_boxes = 0, cap_refit_work = 0;
+    DevBuf<cpt::RefitNode> d_refit_plan;
+    DevBuf<cpt::Box6> d_refit_boxes;
+    DevBuf<uint8_t> d_refit_work;   // an update batch: RefitLeaf records, then the dirty node ids
     float last_update_ms = 0.f;     // host wall time of the last cpt_update_objects[_rebuild]
 
     // material textures (cpt_bind_texture)
-    struct Texture { uint64_t handle; uint32_t* d_texels; int w, h, cols, addr, filter; };
+    struct Texture { uint64_t handle; DevBuf<uint32_t> d_texels; int w, h, cols, addr, filter; };
     std::vector<Texture> textures;
-    TexDesc* d_texdescs = nullptr;
-    int32_t* d_tex_of_mat = nullptr;
-    size_t cap_texdescs = 0, cap_tex_of_mat = 0;
+    DevBuf<TexDesc> d_texdescs;
+    DevBuf<int32_t> d_tex_of_mat;
 
     // environment
-    uint32_t* d_env = nullptr;
+    DevBuf<uint32_t> d_env;
     int env_w = 1, env_h = 1, env_cols = 0;
-    size_t cap_env = 0;
 
-    // frame
+    // frame: the geometry the last cpt_set_frame gave, and what lives and dies with it
     int width = 0, height = 0, n_rows = 0;
     std::vector<int32_t> rows_h;
-    int32_t* d_rows = nullptr;
-    uint32_t* d_rng = nullptr;
-    float4* d_accum = nullptr;
-    float* d_normal = nullptr;
-    float* d_depth = nullptr;
-    bool frame_set = false, rng_set = false;
+    uint64_t frame_gen = 0;           // process-unique id of the current frame layout (cpt_set_frame)
+    Frame frame;
 
-    // rng init
-    uint32_t* d_jumps = nullptr;
-    uint32_t* d_scratch_w = nullptr;
-    uint32_t* d_scratch_m = nullptr;
-
-    unsigned long long* d_stats = nullptr;
-    uint32_t* d_work = nullptr;
-    void* d_sched = nullptr;     // cost schedule: pilot tile costs + sort scratch
-    size_t cap_sched = 0;
-    uint32_t* d_tile_order = nullptr;
-    size_t cap_tile_order = 0;
-    // CPT_SCHEDULE_PREVIOUS: the Weyl plane after the last such render, and the tile order
-    // its draws gave (the next render's dequeue order)
-    uint32_t* d_prev_d = nullptr;
-    uint32_t* d_prev_order = nullptr;
-    bool prev_d_valid = false, prev_order_valid = false;
-    int prev_since_order = 0;   // renders since the CPT_SCHEDULE_PREVIOUS order was rebuilt
-    uint4* d_resume = nullptr;          // tail consolidation: handed-over chains (5 x uint4 each)
-    size_t cap_resume = 0;
-    cpt::WfState wf{};           // wavefront path state (allocated on first use)
-    bool wf_ready = false;
-    float* d_mix = nullptr;      // display running mean (Mix), rgb per pixel of the display band
-    uint8_t* d_bgra = nullptr;   // display frame (band rows)
-    float4* d_dn_sink = nullptr; // k_denoise_strip: where lanes without an output pixel store (DN_SINK_SLOTS)
-    int band_y0 = -1, band_y1 = -1;   // display band the buffers hold
+    DevBuf<uint32_t> d_jumps;    // rng init: the XORWOW jump tables
+    DevBuf<unsigned long long> d_stats;
+    DevBuf<uint32_t> d_work;
+    DevBuf<uint4> d_resume;      // tail consolidation: handed-over chains (5 x uint4 each)
     float last_kernel_ms = 0.f;
     int last_launches = 0;
     // row-tile gather (cpt_gather_rows): per source context, the frame row each of its rows goes
@@ -121,53 +133,32 @@ struct cpt_ctx {
         int src_device = -1;
         bool peer = false;
         int mode = -1;   // last gather: CPT_GATHER_SAME_DEVICE / _PEER / _STAGED
-        int32_t* d_map = nullptr;
+        DevBuf<int32_t> d_map;
     };
     std::vector<GatherMap> gather_maps;
-    float4* d_gather = nullptr;
-    size_t cap_gather = 0;
-    uint64_t frame_gen = 0;           // process-unique id of the current frame layout (cpt_set_frame)
-    hipEvent_t ev_ready = nullptr;    // a gather's source: its queued work
-    hipEvent_t ev_gathered = nullptr; // a gather's destination: the stitch done
-    hipEvent_t ev_caller = nullptr;   // a device copy's caller stream: its queued work
-    hipEvent_t ev_copied = nullptr;   // a device copy: done on the context's stream
+    DevBuf<float4> d_gather;
+    DevEvent ev_ready;    // a gather's source: its queued work
+    DevEvent ev_gathered; // a gather's destination: the stitch done
+    DevEvent ev_caller;   // a device copy's caller stream: its queued work
+    DevEvent ev_copied;   // a device copy: done on the context's stream
     // consolidation test hooks (cpt_set_debug_consolidation)
     uint32_t dbg = 0;
     bool force_staged_gather = false;   // gather test hook (cpt_set_debug_gather)
     int keeper_spin_log2 = 0, publish_wait_log2 = 0;
 
-    hipStream_t stream() const { return user_stream ? user_stream : own_stream; }
+    hipStream_t stream() const { return user_stream ? user_stream : (hipStream_t)own_stream; }
+    size_t npix() const { return (size_t)n_rows * width; }
 };
 
 namespace cpt {
 namespace ctx {
 
-// Records a formatted message on the context (or, without one, for cpt_last_error(NULL)) and
-// returns `code`.
-int fail(cpt_ctx* c, int code, const char* fmt, ...);
-
-#define HIP_TRY(ctx, expr)                                                                             \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail((ctx), e_ == hipErrorOutOfMemory ? CPT_ERR_OUT_OF_MEMORY : CPT_ERR_HIP,        \
-                        "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);           \
-    } while (0)
-
-template <typename T>
-inline int ensure(cpt_ctx* c, T** ptr, size_t* cap, size_t count) {
-    if (*ptr && *cap >= count) return CPT_OK;
-    if (*ptr) { (void)hipFree(*ptr); *ptr = nullptr; *cap = 0; }
-    if (count == 0) return CPT_OK;
-    HIP_TRY(c, hipMalloc((void**)ptr, count * sizeof(T)));
-    *cap = count;
-    return CPT_OK;
-}
-
-void free_frame(cpt_ctx* c);
 // Drain the context's stream, then report a device-side error of the work it ran.
 int check_device_error(cpt_ctx* c);
 int sync_checked(cpt_ctx* c);
+// A device-to-device copy from one of the context's buffers, ordered against the caller's
+// stream without a host wait (cpt_capi.cpp).
+int copy_ordered(cpt_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t caller);
 
 // cpt_scene.cpp
 int material_slot(cpt_ctx* c, const cpt_material& m);

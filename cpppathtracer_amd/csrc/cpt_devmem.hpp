@@ -1,0 +1,104 @@
+// cpt_devmem.hpp — the C-ABI's error helpers (fail, HIP_TRY) and the move-only owners of what a
+// context holds on the device: DevBuf<T> (a unique_ptr with a capacity), DevEvent, DevStream.
+// A default-constructed owner is empty; assigning a fresh one releases what it held.  Host code only.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <utility>
+
+#include "../../include/cpt.h"
+
+namespace cpt {
+namespace ctx {
+
+// Records a formatted message on the context (or, without one, for cpt_last_error(NULL)) and
+// returns `code`.
+int fail(cpt_ctx* c, int code, const char* fmt, ...);
+
+#define HIP_TRY(ctx, expr)                                                                             \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess)                                                                          \
+            return fail((ctx), e_ == hipErrorOutOfMemory ? CPT_ERR_OUT_OF_MEMORY : CPT_ERR_HIP,        \
+                        "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);           \
+    } while (0)
+
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr);
+            cap_ = std::exchange(o.cap_, 0);
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    size_t capacity() const { return cap_; }   // elements
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    // Exactly `count` (> 0) elements in place of what the buffer held; empty on failure.
+    hipError_t alloc(size_t count) {
+        reset();
+        const hipError_t e = hipMalloc((void**)&p_, count * sizeof(T));
+        if (e == hipSuccess) cap_ = count;
+        else p_ = nullptr;
+        return e;
+    }
+    // Room for `count` elements: the allocation is kept when it is large enough, else replaced
+    // by one of exactly `count` (none for 0).  On failure the buffer is empty.
+    int ensure(cpt_ctx* c, size_t count) {
+        if (p_ && cap_ >= count) return CPT_OK;
+        reset();
+        if (count == 0) return CPT_OK;
+        HIP_TRY(c, alloc(count));
+        return CPT_OK;
+    }
+
+private:
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+};
+
+class DevEvent {
+public:
+    DevEvent() = default;
+    DevEvent(DevEvent&& o) noexcept : e_(std::exchange(o.e_, nullptr)) {}
+    DevEvent& operator=(DevEvent&& o) noexcept {
+        std::swap(e_, o.e_);
+        return *this;
+    }
+    ~DevEvent() { if (e_) (void)hipEventDestroy(e_); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e_, flags); }
+    operator hipEvent_t() const { return e_; }
+
+private:
+    hipEvent_t e_ = nullptr;
+};
+
+class DevStream {
+public:
+    DevStream() = default;
+    DevStream(const DevStream&) = delete;
+    DevStream& operator=(const DevStream&) = delete;
+    ~DevStream() { if (s_) (void)hipStreamDestroy(s_); }
+    hipError_t create(unsigned flags) { return hipStreamCreateWithFlags(&s_, flags); }
+    operator hipStream_t() const { return s_; }
+
+private:
+    hipStream_t s_ = nullptr;
+};
+
+}  // namespace ctx
+}  // namespace cpt

@@ -7,13 +7,13 @@
 #include "cpt_device.hpp"
 
 // Per-lane LDS stack entries of the wide walk; the host keeps the binary walk for a tree that
-// could need more (cpt_capi.cpp linearise_wide).
+// could need more (cpt_host_bvh.cpp linearise_wide).
 #define CPT_WSTACK 32
 
 namespace cpt {
 
 // Wide-tree nodes staged in LDS by the LDS kernels (cpt_path.hpp trace_wide); the host numbers
-// a larger tree so that these are its top (cpt_capi.cpp linearise_wide).
+// a larger tree so that these are its top (cpt_host_bvh.cpp linearise_wide).
 constexpr int LDS_TREE_NODES = 512;
 __host__ __device__ __forceinline__ int lds_tree_nodes(int n_wide) { return n_wide < LDS_TREE_NODES ? n_wide : LDS_TREE_NODES; }
 

@@ -91,7 +91,7 @@ __global__ void k_rng_pixels(const uint32_t* __restrict__ rowmats, const uint32_
 // ======================================================================================
 // Device refit (SceneBVH::UpdateObject / UpdateSceneBVH, bvh.cu:122-157).  The reference refits
 // the updated leaf's ancestors on the host and copies the whole node array back to the GPU;
-// here the host only names the updated leaves and their dirty ancestors (cpt_capi.cpp
+// here the host only names the updated leaves and their dirty ancestors (cpt_scene.cpp
 // device_refit) and the boxes are recomputed where the nodes live, for both trees at once:
 // the reference order, the walk tree's eight octant orders, its 4-wide image and leaf array.
 // One thread per node; a launch per height, so a node's children are final before it runs.
@@ -107,7 +107,7 @@ __device__ __forceinline__ void refit_put_prim(Node* n, const Node& v) {
 }
 
 // An internal node's box into one of its copies: octant form for the walk tree's octant
-// orders (cpt_capi.cpp linearise: the planes a ray of the octant enters through in a).
+// orders (cpt_host_bvh.cpp linearise: the planes a ray of the octant enters through in a).
 __device__ __forceinline__ void refit_put_box(Node* n, const Box6& b, int oct) {
     const bool sx = oct & 1, sy = oct & 2, sz = oct & 4;
     n->a0 = sx ? b.hi[0] : b.lo[0]; n->b0 = sx ? b.lo[0] : b.hi[0];
@@ -116,7 +116,7 @@ __device__ __forceinline__ void refit_put_box(Node* n, const Box6& b, int oct) {
 }
 
 // A slot of the 4-wide image (7 x 16 B per node: [min x][max x][min y][max y][min z][max z] of
-// the four slots, then the refs; cpt_capi.cpp linearise_wide).
+// the four slots, then the refs; cpt_host_bvh.cpp linearise_wide).
 __device__ __forceinline__ void refit_put_slot(uint32_t* image, int slot, const Box6& b) {
     uint32_t* q = image + (size_t)(slot >> 2) * 28;
     const int k = slot & 3;

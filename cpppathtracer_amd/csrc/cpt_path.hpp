@@ -233,7 +233,7 @@ __device__ __forceinline__ bool platform_test(const Node& pl, const RayK& ray, f
 }
 
 // One cylinder cap disk (object.cu:52-77).  The reference's `sqrtf(q) < radius` is decided as
-// `q <= bound` with the leaf's precomputed bound (Node::b1 of a cylinder leaf, cpt_capi.cpp
+// `q <= bound` with the leaf's precomputed bound (Node::b1 of a cylinder leaf, cpt_host_bvh.cpp
 // cap_disk_bound): the same decision for every float q, without the correctly rounded square
 // root.
 __device__ __forceinline__ bool cap_test(float cx, float cz, float bound, const RayK& ray, float& tmax, int& kind,
@@ -304,7 +304,7 @@ __device__ __forceinline__ Hit hit_attributes(const Node& nd, const RayK& ray, f
     const v3 pc = h.pos - c;
     if (kind == HK_SPHERE_ROOT1) {
         // (p - c) / radius, each component the IEEE quotient: qdiv with the sphere leaf's double
-        // reciprocal of its radius (Node::b1/b2, cpt_capi.cpp make_node)
+        // reciprocal of its radius (Node::b1/b2, cpt_host_bvh.cpp make_node)
         const double y = __hiloint2double(__float_as_int(nd.b2), __float_as_int(nd.b1));
         h.normal = mk(qdiv(pc.x, nd.b0, y), qdiv(pc.y, nd.b0, y), qdiv(pc.z, nd.b0, y));
     } else {
@@ -416,7 +416,7 @@ __device__ __forceinline__ bool slab_reject(const Node& nd, const RayK& ray, flo
     return lo > hi || lo > tmax || hi < ray.tmin;
 }
 
-// slab_reject<FAST, true> on a walk-tree inner node stored in octant form (cpt_capi.cpp
+// slab_reject<FAST, true> on a walk-tree inner node stored in octant form (cpt_host_bvh.cpp
 // linearise): a.xyz are the planes a ray of the node's octant enters through, b.xyz the ones
 // it leaves through.  For an axis with i != 0 the sign of i is the octant's, so the entry
 // plane's distance is the min of the pair and the exit plane's the max (the subtraction, the
@@ -451,7 +451,7 @@ struct BufSrc {
     }
 };
 
-// The wide tree's compact image (cpt_capi.cpp linearise_wide): 7 x 16 B per node, after the
+// The wide tree's compact image (cpt_host_bvh.cpp linearise_wide): 7 x 16 B per node, after the
 // eight binary octant orders; padded to whole 32-B Nodes.
 __host__ __device__ __forceinline__ int wide_compact_nodes(int n_wide) { return (7 * n_wide + 1) / 2; }
 // Node index of the compact image, and of the wide tree's leaf array after it (the image's
@@ -644,7 +644,7 @@ __device__ __forceinline__ int trace(const SRC& nodes, int n_nodes, const RayK& 
 
 // ======================================================================================
 // The ordered walk on the 4-wide walk tree (DESIGN.md §Ordered walk, Execution).  One iteration reads a
-// 112-B node of the tree's compact image (cpt_capi.cpp linearise_wide) and tests its four
+// 112-B node of the tree's compact image (cpt_host_bvh.cpp linearise_wide) and tests its four
 // children's boxes with the conservative octant-form slab; the nearest hit child is taken
 // next, the other hits go onto a per-lane stack in LDS (far ones first).  Leaves are parked
 // and tested in wave-wide rounds: a lane that meets a leaf parks it and walks on; it stops at
@@ -668,7 +668,7 @@ typedef __attribute__((address_space(3))) int16_t lds_i16;
 // The compact image's first LDS_TREE_NODES nodes are staged in LDS (k_megakernel<..., LDST>,
 // k_wf_extend<..., LDST>); a larger tree's remaining nodes are read from the image in global
 // memory (L2-resident).  The host numbers the wide nodes largest box first, parents before
-// children (cpt_capi.cpp linearise_wide), so the LDS part is the top of the tree, the part
+// children (cpt_host_bvh.cpp linearise_wide), so the LDS part is the top of the tree, the part
 // every ray walks.
 // (LDS_TREE_NODES, lds_tree_nodes: cpt_internal.hpp)
 
@@ -742,7 +742,7 @@ __device__ __forceinline__ uint32_t wide_pair(const f2v e[3], const f2v x[3], co
     return (pa ? 1u : 0u) | (pb ? 2u : 0u);
 }
 
-// Child refs (the image's int16 words, cpt_capi.cpp linearise_wide): >= 0 a wide node, -1 none,
+// Child refs (the image's int16 words, cpt_host_bvh.cpp linearise_wide): >= 0 a wide node, -1 none,
 // <= -2 leaf i of the leaf array as ~(i + 1).  The host keeps the ranges within 15 bits, so the
 // LDS stack holds 16-bit entries (BLK lanes x CPT_WSTACK x 2 B per block).
 // A lane's wide walk in progress, kept across rounds of the megakernel when the walk is

@@ -175,13 +175,13 @@ int upload_scene(cpt_ctx* c) {
                     (size_t)INT32_MAX / sizeof(Node));
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, &c->d_nodes, &c->cap_nodes, std::max<size_t>(1, c->lin.size()))) != CPT_OK) return rc;
+    if ((rc = c->d_nodes.ensure(c, std::max<size_t>(1, c->lin.size()))) != CPT_OK) return rc;
     hipStream_t s = c->stream();
     if (!c->lin.empty())
         HIP_TRY(c, hipMemcpyAsync(c->d_nodes, c->lin.data(), c->lin.size() * sizeof(Node), hipMemcpyHostToDevice, s));
     if (!c->refit_plan.empty()) {   // the device refit's plan and the boxes as built
-        if ((rc = ensure(c, &c->d_refit_plan, &c->cap_refit_plan, c->refit_plan.size())) != CPT_OK) return rc;
-        if ((rc = ensure(c, &c->d_refit_boxes, &c->cap_refit_boxes, c->refit_boxes.size())) != CPT_OK) return rc;
+        if ((rc = c->d_refit_plan.ensure(c, c->refit_plan.size())) != CPT_OK) return rc;
+        if ((rc = c->d_refit_boxes.ensure(c, c->refit_boxes.size())) != CPT_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->d_refit_plan, c->refit_plan.data(), c->refit_plan.size() * sizeof(cpt::RefitNode),
                                   hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(c->d_refit_boxes, c->refit_boxes.data(), c->refit_boxes.size() * sizeof(cpt::Box6),
@@ -199,11 +199,11 @@ int upload_scene(cpt_ctx* c) {
 int upload_materials(cpt_ctx* c) {
     int rc;
     hipStream_t s = c->stream();
-    if (c->d_mats && c->cap_mats < c->mats_h.size()) {
+    if (c->d_mats && c->d_mats.capacity() < c->mats_h.size()) {
         // a grown array: the kernels of earlier renders may still read the old one
         HIP_TRY(c, hipStreamSynchronize(s));
     }
-    if ((rc = ensure(c, &c->d_mats, &c->cap_mats, std::max<size_t>(1, c->mats_h.size()))) != CPT_OK) return rc;
+    if ((rc = c->d_mats.ensure(c, std::max<size_t>(1, c->mats_h.size()))) != CPT_OK) return rc;
     if (!c->mats_h.empty()) {
         // textured materials: resolve their handles against the bound textures
         std::vector<int32_t> tex_of_mat(c->mats_h.size(), -1);
@@ -221,10 +221,10 @@ int upload_materials(cpt_ctx* c) {
             std::vector<TexDesc> descs(c->textures.size());
             for (size_t t = 0; t < descs.size(); ++t) {
                 const auto& x = c->textures[t];
-                descs[t] = TexDesc{x.d_texels, x.w, x.h, x.cols, x.addr, x.filter, 0};
+                descs[t] = TexDesc{x.d_texels.get(), x.w, x.h, x.cols, x.addr, x.filter, 0};
             }
-            if ((rc = ensure(c, &c->d_texdescs, &c->cap_texdescs, descs.size())) != CPT_OK) return rc;
-            if ((rc = ensure(c, &c->d_tex_of_mat, &c->cap_tex_of_mat, tex_of_mat.size())) != CPT_OK) return rc;
+            if ((rc = c->d_texdescs.ensure(c, descs.size())) != CPT_OK) return rc;
+            if ((rc = c->d_tex_of_mat.ensure(c, tex_of_mat.size())) != CPT_OK) return rc;
             HIP_TRY(c, hipMemcpyAsync(c->d_texdescs, descs.data(), descs.size() * sizeof(TexDesc), hipMemcpyHostToDevice, s));
             HIP_TRY(c, hipMemcpyAsync(c->d_tex_of_mat, tex_of_mat.data(), tex_of_mat.size() * sizeof(int32_t),
                                       hipMemcpyHostToDevice, s));
@@ -282,7 +282,7 @@ int device_refit(cpt_ctx* c, int n, const int* indices, bool mats_changed) {
     if (!dirty.empty()) std::memcpy(work.data() + rec_bytes, dirty.data(), dirty.size() * sizeof(int32_t));
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, &c->d_refit_work, &c->cap_refit_work, work.size())) != CPT_OK) return rc;
+    if ((rc = c->d_refit_work.ensure(c, work.size())) != CPT_OK) return rc;
     uint8_t* const d_work = c->d_refit_work;
     hipStream_t s = c->stream();
     HIP_TRY(c, hipMemcpyAsync(d_work, work.data(), work.size(), hipMemcpyHostToDevice, s));
@@ -462,7 +462,7 @@ int cpt_set_env_texture(cpt_ctx* c, const uint8_t* rgba, int logical_width, int 
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_set_env_texture: bad geometry %dx%d cols %d", logical_width, height, valid_cols);
     HIP_TRY(c, hipSetDevice(c->device));
     size_t n = (size_t)valid_cols * height;
-    int rc = ensure(c, &c->d_env, &c->cap_env, std::max<size_t>(1, n));
+    int rc = c->d_env.ensure(c, std::max<size_t>(1, n));
     if (rc != CPT_OK) return rc;
     if (n) HIP_TRY(c, hipMemcpy(c->d_env, rgba, n * 4, hipMemcpyHostToDevice));
     c->env_w = logical_width;
@@ -481,17 +481,18 @@ int cpt_bind_texture(cpt_ctx* c, uint64_t handle, const uint8_t* rgba, int logic
                     height, valid_cols, address_mode, filter_mode);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)valid_cols * height;
-    uint32_t* d = nullptr;
-    HIP_TRY(c, hipMalloc((void**)&d, std::max<size_t>(1, n) * 4));
+    DevBuf<uint32_t> d;
+    if (int rc = d.ensure(c, std::max<size_t>(1, n))) return rc;
     if (n) {
         hipError_t e = hipMemcpy(d, rgba, n * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(c, CPT_ERR_HIP, "cpt_bind_texture: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(c, CPT_ERR_HIP, "cpt_bind_texture: %s", hipGetErrorString(e));
     }
-    cpt_ctx::Texture t{handle, d, logical_width, height, valid_cols, address_mode, filter_mode};
-    bool replaced = false;
+    cpt_ctx::Texture t{handle, std::move(d), logical_width, height, valid_cols, address_mode, filter_mode};
+    cpt_ctx::Texture* slot = nullptr;
     for (auto& x : c->textures)
-        if (x.handle == handle) { (void)hipFree(x.d_texels); x = t; replaced = true; }
-    if (!replaced) c->textures.push_back(t);
+        if (x.handle == handle) slot = &x;
+    if (slot) *slot = std::move(t);
+    else c->textures.push_back(std::move(t));
     return c->scene_set ? upload_scene(c) : CPT_OK;   // re-prepare the materials
 }
 

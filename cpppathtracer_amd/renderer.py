@@ -176,8 +176,9 @@ class Renderer:
         self._check(self._L.cpt_render(self._ctx, _p(c), spp, max_depth, f))
 
     def tile_costs(self, cam, passes, max_depth, ordered=True):
-        """The cost schedule's pilot alone (cpt_tile_costs): each 8x8 tile's work over `passes`
-        passes from the current RNG states (nothing written back), [tiles_y, tiles_x] uint32."""
+        """The cost schedule's pilot alone (cpt_tile_costs): the work of each 8x8 tile's heaviest
+        pixel (the maximum over the tile's pixels, not their sum) over `passes` passes from the
+        current RNG states (nothing written back), [tiles_y, tiles_x] uint32."""
         c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
         ty, tx = (self.n_rows + 7) // 8, (self.width + 7) // 8
         out = np.zeros((ty, tx), dtype=np.uint32)

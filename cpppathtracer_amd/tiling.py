@@ -51,7 +51,9 @@ def rows_of_owner(height: int, owner, rank: int, block: int = BLOCK_ROWS) -> np.
 
 def block_costs_from_tiles(tile_costs, block: int = BLOCK_ROWS) -> np.ndarray:
     """Per row block cost from the pilot's per 8x8 tile costs (Renderer.tile_costs of the whole
-    frame): a block of 8 rows is one row of tiles."""
+    frame): a block of 8 rows is one row of tiles.  A tile's cost is its heaviest pixel's work, so
+    a block's cost, and the load the balanced partition (lpt_owner) evens out, is a sum of
+    per-tile maxima, not the block's total work."""
     assert block == 8, "the pilot's tiles are 8 rows high"
     return np.asarray(tile_costs, dtype=np.int64).sum(axis=1)
 

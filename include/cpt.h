@@ -267,10 +267,11 @@ int cpt_read_aux(cpt_ctx* ctx, float* normal3, float* depth); /* either may be N
 int cpt_write_accum(cpt_ctx* ctx, const float* rgba);
 int cpt_write_aux(cpt_ctx* ctx, const float* normal3, const float* depth);
 /* The cost schedule's pilot alone (for cost-balanced row partitions across ranks, tiling.py):
- * `passes` passes from the context's current RNG states (nothing is written back), each 8x8 tile's
- * work -- segments + node visits + primitive tests, the walk of `flags`' CPT_TRAVERSAL_* bits --
- * into out[tile] (tiles row-major over the context's rows: ((n_rows+7)/8) x ((width+7)/8);
- * n_out at least that).  Synchronous. */
+ * `passes` passes from the context's current RNG states (nothing is written back), the work of
+ * each 8x8 tile's heaviest pixel -- its segments + node visits + primitive tests, the walk of
+ * `flags`' CPT_TRAVERSAL_* bits; the maximum over the tile's pixels, not their sum -- into
+ * out[tile] (tiles row-major over the context's rows: ((n_rows+7)/8) x ((width+7)/8); n_out at
+ * least that).  Synchronous. */
 int cpt_tile_costs(cpt_ctx* ctx, const cpt_camera* cam, int passes, int max_depth, uint32_t flags, uint32_t* out,
                    size_t n_out);
 /* Device-to-device copy of the accumulator (e.g. into an RCCL send buffer), ordered against the
@@ -383,7 +384,7 @@ int cpt_measure_read_bandwidth(cpt_ctx* ctx, size_t bytes, int iters, float* gbp
  * (k_read_pattern<bpl>) per shape: the known byte counts a rocprofv3 FETCH_SIZE pass is calibrated
  * against (tools/fetch_calibration.py). */
 int cpt_measure_read_pattern(cpt_ctx* ctx, int bytes_per_lane, size_t bytes, int iters, float* gbps);
-/* Host-only test hook (no GPU): the cap-disk bound a cylinder leaf carries (cpt_capi.cpp
+/* Host-only test hook (no GPU): the cap-disk bound a cylinder leaf carries (cpt_host_bvh.cpp
  * cap_disk_bound), the largest float c with  sqrtf(q) < radius  <=>  q <= c  for every float
  * q; the kernels decide the reference's cap test (object.cu:52-77) with it. */
 int cpt_cap_disk_bound(float radius, float* out);

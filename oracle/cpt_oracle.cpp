@@ -625,7 +625,7 @@ void build_bvh(Bvh& bvh, const Object* objs, int n) {
 
 // Walk tree of the diagnostic ordered walk: platforms (unbounded) are tested first; the other
 // primitives get a binned-SAH tree (16 bins per axis, one primitive per leaf), built with the
-// same float operations as libcpt's host builder (cpt_capi.cpp, namespace sah).
+// same float operations as libcpt's host builder (cpt_host_bvh.cpp, namespace sah).
 namespace walk_sah {
 constexpr int NB = 16;
 inline float comp(f3 v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }

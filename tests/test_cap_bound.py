@@ -1,4 +1,4 @@
-"""The cylinder cap test's bound (cpt_capi.cpp cap_disk_bound, cpt_path.hpp cap_test): the
+"""The cylinder cap test's bound (cpt_host_bvh.cpp cap_disk_bound, cpt_path.hpp cap_test): the
 kernels decide the reference's `sqrtf(q) < radius` (object.cu:52-77) as `q <= bound`.  Host
 only: the bound comes from libcpt.so's test hook, the truth from numpy's correctly rounded
 float32 sqrt, over radii of every magnitude and q at and around each bound."""
