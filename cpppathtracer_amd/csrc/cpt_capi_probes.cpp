@@ -1,6 +1,6 @@
 // cpt_capi_probes.cpp — the C-ABI's diagnostic entry points: the math batch, the read-bandwidth
-// probes, the device self-tests, the timeline readout and the host-only cap-disk bound.  Their
-// temporaries are local owners, so every early return releases them.
+// probes, the device self-tests, the timeline and node-memory readouts and the host-only cap-disk
+// bound.  Their temporaries are local owners, so every early return releases them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,7 +39,20 @@ int cpt_debug_timeline(cpt_ctx* c, uint64_t* out, int n) {
     return CPT_OK;
 }
 
-int cpt_math_batch(cpt_ctx* c, int op, const float* a, const float* b, float* out, size_t n) {
+int cpt_debug_read_nodes(cpt_ctx* c, void* out, size_t capacity_bytes, size_t* n_bytes) {
+    if (!c || !n_bytes) return CPT_ERR_INVALID_ARG;
+    if (!c->scene_set) return fail(c, CPT_ERR_STATE, "cpt_debug_read_nodes: cpt_set_scene first");
+    const size_t bytes = c->lin.size() * sizeof(cpt::Node);   // what upload_scene copied: every order in use
+    *n_bytes = bytes;
+    if (!out || bytes == 0) return CPT_OK;
+    if (capacity_bytes < bytes)
+        return fail(c, CPT_ERR_INVALID_ARG, "cpt_debug_read_nodes: %zu < %zu bytes", capacity_bytes, bytes);
+    if (int rc = sync_checked(c)) return rc;
+    HIP_TRY(c, hipMemcpy(out, c->d_nodes, bytes, hipMemcpyDeviceToHost));
+    return CPT_OK;
+}
+
+int cpt_math_batch(cpt_ctx* c, int op,const float* a, const float* b, float* out, size_t n) {
     if (!c || !a || !b || !out) return CPT_ERR_INVALID_ARG;
     if (n == 0) return CPT_OK;
     HIP_TRY(c, hipSetDevice(c->device));

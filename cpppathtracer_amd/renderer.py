@@ -302,6 +302,16 @@ class Renderer:
         self._check(self._L.cpt_get_walk_info(self._ctx, _p(out)))
         return dict(zip(("n_bvh", "n_walk", "n_wide", "n_unb"), (int(x) for x in out)))
 
+    def read_nodes(self):
+        """DIAGNOSTIC: the device's node memory (cpt_debug_read_nodes) as uint8: the reference
+        order, the eight octant orders, the 4-wide image and its leaf array (walk_info's counts)."""
+        n = ctypes.c_size_t(0)
+        self._check(self._L.cpt_debug_read_nodes(self._ctx, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        if n.value:
+            self._check(self._L.cpt_debug_read_nodes(self._ctx, _p(out), out.size, ctypes.byref(n)))
+        return out
+
     def measure_read_pattern(self, bytes_per_lane, nbytes=1 << 30, iters=1):
         """DIAGNOSTIC: GB/s of a streaming read in one of the display kernel's access shapes
         (cpt_measure_read_pattern: 4, 12 or 16 bytes per lane)."""

@@ -330,6 +330,15 @@ int cpt_get_execdiag_counters(cpt_ctx* ctx, uint64_t* out64);
  * the walk tree.  With [2] > 0, the `nodes` counter of an ordered render counts 4-wide node
  * visits. */
 int cpt_get_walk_info(cpt_ctx* ctx, int32_t* out4);
+/* DIAGNOSTIC: the device's node memory as the kernels read it, copied to `out` after the
+ * context's queued work (a device refit included) has finished: with cpt_get_walk_info's counts,
+ * [0] reference-order nodes of 32 B, then eight octant orders of [1] nodes each, then the 4-wide
+ * image ([2] x 112 B, padded to a multiple of 32 B) and its leaf array (32-B nodes to the end;
+ * image and leaves only when [2] > 0).  *n_bytes receives the size; out == NULL asks for the
+ * size alone, and a capacity_bytes below it is CPT_ERR_INVALID_ARG (nothing written).  Launches
+ * no kernel and changes no state.  No reference counterpart: a test hook for the device refit
+ * (an addition to the ABI: CPT_ABI_VERSION stays 1). */
+int cpt_debug_read_nodes(cpt_ctx* ctx, void* out, size_t capacity_bytes, size_t* n_bytes);
 /* Device time of the last cpt_render (HIP events on the launch stream); waits for it. */
 int cpt_last_render_ms(cpt_ctx* ctx, float* ms);
 /* Average device time of one launch of the last cpt_render's dominant kernel: the megakernel
