@@ -76,6 +76,7 @@ PROTOTYPES = {
     "cpt_math_batch": (_I, [_P, _I, _P, _P, _P, _SZ]),
     "cpt_selftest_qdiv": (_I, [_P, _I, _U64, _U64, _P, _I]),
     "cpt_set_debug_consolidation": (_I, [_P, _U32, _I, _I]),
+    "cpt_set_debug_grid": (_I, [_P, _I, _I]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1

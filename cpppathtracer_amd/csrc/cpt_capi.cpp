@@ -346,6 +346,7 @@ static void fill_params(cpt_ctx* c, const cpt_camera* cam, int spp, int max_dept
     if (const char* e = getenv("CPT_REPLICATE")) p.replicate = std::max(1, std::min(64, atoi(e)));
 #endif
     if (p.replicate < 1) p.replicate = 1;
+    if (c->dbg_lanes_per_wave > 0) p.lanes = c->dbg_lanes_per_wave;   // TEST HOOK cpt_set_debug_grid
     p.error = c->d_work + 4;
     p.dbg = c->dbg;
     p.keeper_spin_log2 = c->keeper_spin_log2;
@@ -436,7 +437,8 @@ static int cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStream_t
     int rc;
     if ((rc = f.d_sched.ensure(c, cpt::tile_schedule_scratch_bytes(c->width, c->n_rows))) != CPT_OK) return rc;
     if ((rc = f.d_tile_order.ensure(c, n_tiles(c))) != CPT_OK) return rc;
-    HIP_TRY(c, cpt::launch_tile_schedule(p, passes, f.d_sched, f.d_sched.capacity(), f.d_tile_order, s));
+    HIP_TRY(c, cpt::launch_tile_schedule(p, passes, f.d_sched, f.d_sched.capacity(), f.d_tile_order,
+                                         c->dbg_max_workgroups, s));
     return CPT_OK;
 }
 
@@ -505,7 +507,7 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
         }
         if ((rc = consolidation_slab(c, p, spp, flags)) != CPT_OK) return rc;
         HIP_TRY(c, hipEventRecord(c->ev_main, s));
-        HIP_TRY(c, cpt::launch_megakernel(p, (flags & CPT_RENDER_STATS) != 0, aux, s));
+        HIP_TRY(c, cpt::launch_megakernel(p, (flags & CPT_RENDER_STATS) != 0, aux, c->dbg_max_workgroups, s));
         HIP_TRY(c, hipEventRecord(c->ev_stop, s));
         if (previous && (rc = previous_order_refresh(c, p, s)) != CPT_OK) return rc;
     }
@@ -547,6 +549,14 @@ int cpt_set_debug_consolidation(cpt_ctx* c, uint32_t flags, int keeper_spin_log2
     c->dbg = flags;
     c->keeper_spin_log2 = keeper_spin_log2;
     c->publish_wait_log2 = publish_wait_log2;
+    return CPT_OK;
+}
+
+int cpt_set_debug_grid(cpt_ctx* c, int max_workgroups, int lanes_per_wave) {
+    if (!c || max_workgroups < 0 || lanes_per_wave < 0 || lanes_per_wave > 64)
+        return c ? fail(c, CPT_ERR_INVALID_ARG, "cpt_set_debug_grid: bad arguments") : CPT_ERR_INVALID_ARG;
+    c->dbg_max_workgroups = max_workgroups;
+    c->dbg_lanes_per_wave = lanes_per_wave;
     return CPT_OK;
 }
 

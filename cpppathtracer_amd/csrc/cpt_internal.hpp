@@ -83,13 +83,15 @@ enum : uint32_t {
 // megakernel sums each 8x8 tile's work, then `order` (one u32 per tile) gets the tiles
 // heaviest first.  `scratch` holds tile_schedule_scratch_bytes() bytes.
 size_t tile_schedule_scratch_bytes(int width, int n_rows);
-hipError_t launch_cost_pilot(const KParams& p, hipStream_t stream);   // cpt_megakernel.hip: the pilot's launch
+// (max_workgroups: the persistent grid's cap, a launcher argument and not a kernel parameter;
+// 0 = none.  TEST HOOK cpt_set_debug_grid.)
+hipError_t launch_cost_pilot(const KParams& p, int max_workgroups, hipStream_t stream);   // cpt_megakernel.hip: the pilot's launch
 // CPT_SCHEDULE_PREVIOUS: each 8x8 tile's RNG draws since `d_prev` (the Weyl plane d of the
 // states, planar [5] of p.rng), then d_prev := d; the tiles sorted heaviest first into `order`.
 hipError_t launch_tile_order_from_draws(const KParams& p, uint32_t* d_prev, void* scratch, size_t scratch_bytes,
                                         uint32_t* order, hipStream_t stream);
 hipError_t launch_tile_schedule(const KParams& p, int passes, void* scratch, size_t scratch_bytes, uint32_t* order,
-                                hipStream_t stream);
+                                int max_workgroups, hipStream_t stream);
 
 // Wavefront path state (cpt_wavefront.hip): SoA float4 arrays indexed by QUEUE SLOT + queues.
 // The carried state is double-buffered: bounce b reads buffer b & 1 at its queue slot and shade
@@ -131,7 +133,7 @@ hipError_t launch_refit(const RefitLeaf* leaves_in, int n_leaves, const int32_t*
                         int n_levels, int n_ref, const RefitNode* nodes_plan, Box6* boxes, Node* nodes, uint32_t* image,
                         Node* leaves, hipStream_t stream);
 
-hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, hipStream_t stream);
+hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, int max_workgroups, hipStream_t stream);
 hipError_t launch_wavefront(const KParams& p, WfState& w, bool stats, bool aux, hipStream_t stream, int* launches);
 hipError_t wavefront_build_ident(const KParams& p, WfState& w, hipStream_t stream);
 hipError_t launch_prepare_materials(Mat* mats, const int32_t* tex_of_mat, const TexDesc* texs, int n,

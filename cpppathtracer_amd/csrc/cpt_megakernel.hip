@@ -645,7 +645,7 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
 // Host-side launchers (called from cpt_capi.cpp).
 // ======================================================================================
 template <bool S, bool A, bool P, bool T, bool C = false, bool H = false>
-static hipError_t launch_mk(const KParams& p, hipStream_t stream) {
+static hipError_t launch_mk(const KParams& p, int max_workgroups, hipStream_t stream) {
     static int blocks_per_cu = -1, cus = 0;
     constexpr int block = mk_block<T>();
     if (blocks_per_cu < 0) {
@@ -663,6 +663,9 @@ static hipError_t launch_mk(const KParams& p, hipStream_t stream) {
     const int per_wave = std::max(1, p.lanes / std::max(1, p.replicate));
     long long want = (tiles * 64 * ((64 + per_wave - 1) / per_wave) + block - 1) / block;
     long long grid = std::min<long long>(want, (long long)blocks_per_cu * cus);
+    // TEST HOOK (cpt_set_debug_grid): fewer workgroups, so that lanes take several pixels in turn
+    // on small frames; the kernel's own gridDim.x follows
+    if (max_workgroups > 0) grid = std::min<long long>(grid, max_workgroups);
     if (grid < 1) return hipSuccess;
     hipLaunchKernelGGL((k_megakernel<S, A, P, T, C, H>), dim3((unsigned)grid), dim3(block), 0, stream, p);
     return hipGetLastError();
@@ -673,32 +676,34 @@ static hipError_t launch_mk(const KParams& p, hipStream_t stream) {
 static bool use_lds_tree(const KParams& p) { return p.ordered == 1 && p.n_wide > 0; }
 
 template <bool S, bool A, bool P, bool H>
-static hipError_t launch_mk_lds(const KParams& p, hipStream_t stream) {
+static hipError_t launch_mk_lds(const KParams& p, int max_workgroups, hipStream_t stream) {
     if constexpr (!P && ho_slots<mk_block<true>()>() > 0) {
-        if (p.resume) return launch_mk<S, A, P, true, true, H>(p, stream);   // tail consolidation
+        if (p.resume) return launch_mk<S, A, P, true, true, H>(p, max_workgroups, stream);   // tail consolidation
     }
-    return launch_mk<S, A, P, true, false, H>(p, stream);
+    return launch_mk<S, A, P, true, false, H>(p, max_workgroups, stream);
 }
 
 template <bool S, bool A, bool P>
-static hipError_t launch_mk_any(const KParams& p, hipStream_t stream) {
-    if (!use_lds_tree(p)) return launch_mk<S, A, P, false>(p, stream);
-    if (p.n_wide > LDS_TREE_NODES) return launch_mk_lds<S, A, P, true>(p, stream);
-    return launch_mk_lds<S, A, P, false>(p, stream);
+static hipError_t launch_mk_any(const KParams& p, int max_workgroups, hipStream_t stream) {
+    if (!use_lds_tree(p)) return launch_mk<S, A, P, false>(p, max_workgroups, stream);
+    if (p.n_wide > LDS_TREE_NODES) return launch_mk_lds<S, A, P, true>(p, max_workgroups, stream);
+    return launch_mk_lds<S, A, P, false>(p, max_workgroups, stream);
 }
 
-hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, hipStream_t stream) {
+hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, int max_workgroups, hipStream_t stream) {
     if (p.width <= 0 || p.n_rows <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(p.work, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    if (stats && aux) return launch_mk_any<true, true, false>(p, stream);
-    if (stats) return launch_mk_any<true, false, false>(p, stream);
-    if (aux) return launch_mk_any<false, true, false>(p, stream);
-    return launch_mk_any<false, false, false>(p, stream);
+    if (stats && aux) return launch_mk_any<true, true, false>(p, max_workgroups, stream);
+    if (stats) return launch_mk_any<true, false, false>(p, max_workgroups, stream);
+    if (aux) return launch_mk_any<false, true, false>(p, max_workgroups, stream);
+    return launch_mk_any<false, false, false>(p, max_workgroups, stream);
 }
 
 // The cost schedule's pilot (cpt_schedule.hip launch_tile_schedule): the PROBE kernels.
-hipError_t launch_cost_pilot(const KParams& p, hipStream_t stream) { return launch_mk_any<false, false, true>(p, stream); }
+hipError_t launch_cost_pilot(const KParams& p, int max_workgroups, hipStream_t stream) {
+    return launch_mk_any<false, false, true>(p, max_workgroups, stream);
+}
 
 // DIAGNOSTIC (CPT_TIMELINE builds): copy the lane-occupancy timeline out (n words, at most
 // timeline::TL_WORDS) and clear it for the next render; other builds: hipErrorNotSupported.

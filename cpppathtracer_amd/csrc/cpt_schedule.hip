@@ -103,7 +103,7 @@ hipError_t launch_tile_order_from_draws(const KParams& p, uint32_t* d_prev, void
 }
 
 hipError_t launch_tile_schedule(const KParams& p0, int passes, void* scratch, size_t scratch_bytes, uint32_t* order,
-                                hipStream_t stream) {
+                                int max_workgroups, hipStream_t stream) {
     const int n = ((p0.width + 7) / 8) * ((p0.n_rows + 7) / 8);
     if (n <= 0) return hipSuccess;
     const TileScratch s = carve_tile_scratch(scratch, scratch_bytes, n);
@@ -115,7 +115,7 @@ hipError_t launch_tile_schedule(const KParams& p0, int passes, void* scratch, si
     p.tile_cost = s.cost;
     p.tile_order = nullptr;
     p.accumulate = 0;
-    e = launch_cost_pilot(p, stream);
+    e = launch_cost_pilot(p, max_workgroups, stream);
     if (e != hipSuccess) return e;
     return sort_tiles_by_cost(s, n, order, stream);
 }

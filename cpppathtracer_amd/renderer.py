@@ -330,6 +330,12 @@ class Renderer:
         """TEST HOOK (cpt_set_debug_consolidation): provoke the tail consolidation's error paths."""
         self._check(self._L.cpt_set_debug_consolidation(self._ctx, flags, keeper_spin_log2, publish_wait_log2))
 
+    def set_debug_grid(self, max_workgroups=0, lanes_per_wave=0):
+        """TEST HOOK (cpt_set_debug_grid): cap the megakernel's persistent grid at `max_workgroups`
+        workgroups and let only the first `lanes_per_wave` lanes of a wave take pixels, so that
+        small frames exercise the lane refill; 0, 0 (the default) is normal operation."""
+        self._check(self._L.cpt_set_debug_grid(self._ctx, int(max_workgroups), int(lanes_per_wave)))
+
     def reset_stats(self):
         self._check(self._L.cpt_reset_stats(self._ctx))
 

@@ -438,6 +438,21 @@ int cpt_selftest_qdiv(cpt_ctx* ctx, int which, uint64_t n, uint64_t seed, uint64
  * idle-spin limit and the hand-over wait as log2 (0 = the defaults, 26 and 22).  A render that
  * trips either limit must end with CPT_ERR_DEVICE. */
 int cpt_set_debug_consolidation(cpt_ctx* ctx, uint32_t flags, int keeper_spin_log2, int publish_wait_log2);
+/* TEST HOOK that caps the megakernel's persistent grid (0, 0 = normal operation, the default), so
+ * that frames small enough for the scalar oracle make every lane take several pixels in turn.
+ * max_workgroups > 0: the render's launch and the cost pilot's (cpt_render with
+ * CPT_SCHEDULE_COST, cpt_tile_costs) have at most that many workgroups (1024 lanes each with the
+ * 4-wide walk's LDS image, 256 without).  lanes_per_wave > 0: only the first lanes_per_wave lanes
+ * of each wave take pixels and handed-over chains; the others stay idle.  Every kernel
+ * instantiation is well defined for 1 <= lanes_per_wave < 64: the thresholds of the wide walk's
+ * leaf rounds and of the deferred sky fetches are shares of the lanes at work, a walk is
+ * suspended only after 40 lanes of its wave have finished theirs (never, below 41 lanes), the
+ * static first take switches itself off, and a retiring wave hands over at most as many chains as
+ * it holds (the levels below then queue chains they have no idle lane for yet, and take them as
+ * lanes fall idle).  The image, the RNG end states and every counter the walk defines per ray are
+ * unchanged; the render is slower.  The wavefront path has no persistent grid and ignores the
+ * hook.  Negative values and lanes_per_wave > 64: CPT_ERR_INVALID_ARG. */
+int cpt_set_debug_grid(cpt_ctx* ctx, int max_workgroups, int lanes_per_wave);
 
 #ifdef __cplusplus
 }  /* extern "C" */

@@ -480,8 +480,12 @@ def test_update_object_refit(gpu, oracle_mod, sky, path):
     """SceneBVH::UpdateObject (bvh.cu:122-157): the leaf takes the new object, its ancestors'
     boxes are refit and the topology is kept.  Moves a sphere far out (boxes grow), shrinks a
     cylinder, swaps a material; the render after the edits matches the oracle's refit BVH."""
+    _update_object_refit(gpu, oracle_mod, sky, path, 48, 32)
+
+
+def _update_object_refit(gpu, oracle_mod, sky, path, W, H):
     objs = scenes.scene_s1000(n=40)
-    W, H, spp, depth = 48, 32, 2, 8
+    spp, depth = 2, 8
     cam = camera_get_copy(scenes.camera_for(W, H))
     edits = []
     sph = int(np.flatnonzero(objs["type"] == 0)[3])
