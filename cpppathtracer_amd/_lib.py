@@ -77,6 +77,10 @@ PROTOTYPES = {
     "cpt_selftest_qdiv": (_I, [_P, _I, _U64, _U64, _P, _I]),
     "cpt_set_debug_consolidation": (_I, [_P, _U32, _I, _I]),
     "cpt_set_debug_grid": (_I, [_P, _I, _I]),
+    "cpt_render_adaptive": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _U32]),
+    "cpt_read_noise": (_I, [_P, _P, _SZ]),
+    "cpt_adaptive_info": (_I, [_P, _P, _P, _I, _P]),
+    "cpt_adaptive_decide_host": (_I, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libcpt.so")
 SOURCES = [
     os.path.join(CSRC, "cpt_megakernel.hip"),
     os.path.join(CSRC, "cpt_schedule.hip"),
+    os.path.join(CSRC, "cpt_adaptive.hip"),
     os.path.join(CSRC, "cpt_display.hip"),
     os.path.join(CSRC, "cpt_selftest.hip"),
     os.path.join(CSRC, "cpt_kernels.hip"),
@@ -23,6 +24,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_capi_gather.cpp"),
     os.path.join(CSRC, "cpt_capi_display.cpp"),
     os.path.join(CSRC, "cpt_capi_probes.cpp"),
+    os.path.join(CSRC, "cpt_capi_adaptive.cpp"),
     os.path.join(CSRC, "cpt_scene.cpp"),
     os.path.join(CSRC, "cpt_host_bvh.cpp"),
     os.path.join(CSRC, "cpt_host_rng.cpp"),

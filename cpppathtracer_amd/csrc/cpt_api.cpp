@@ -603,6 +603,40 @@ bool PathTracer::Render(int spp, bool accumulate) {
     return RenderPass(cma, spp, accumulate);
 }
 
+bool PathTracer::RenderAdaptive(int min_spp, int max_spp, int batch, float rel_error, int* rounds,
+                                uint64_t* passes_done) {
+    if (!camera_) {
+        err_ = "RenderAdaptive: SetCamera first";
+        return false;
+    }
+    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
+    MotionalCamera cma = camera_->GetCopy();
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!SyncScene() || !EnsureFrame(cma)) return false;
+    if (frame_) {   // row tiles stop independently; their rounds are not stitched
+        err_ = "RenderAdaptive: one device only";
+        return false;
+    }
+    cpt_ctx* ctx = tiles_[0].ctx;
+    const uint32_t flags = CPT_RENDER_AUX | (ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) |
+                           (max_spp >= 64 ? CPT_SCHEDULE_COST : 0u);
+    if (cpt_render_adaptive(ctx, reinterpret_cast<const cpt_camera*>(&cma), min_spp, max_spp, batch, rel_error,
+                            (int)max_recursion_depth_, flags) != CPT_OK)
+        return Fail("cpt_render_adaptive", ctx);
+    if (cpt_adaptive_info(ctx, rounds, nullptr, 0, passes_done) != CPT_OK) return Fail("cpt_adaptive_info", ctx);
+    return true;
+}
+
+bool PathTracer::ReadNoise(float* rel) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!FrameCtx() || width_ == 0 || frame_) {
+        err_ = "ReadNoise: RenderAdaptive first";
+        return false;
+    }
+    if (cpt_read_noise(FrameCtx(), rel, (size_t)width_ * height_) != CPT_OK) return Fail("cpt_read_noise");
+    return true;
+}
+
 bool PathTracer::ReadRadiance(std::vector<float>& rgb) {
     std::lock_guard<std::mutex> lk(mu_);
     if (!FrameCtx() || width_ == 0) {

@@ -1,7 +1,7 @@
 // cpt_capi.cpp — implementation of the C-ABI in include/cpt.h: contexts, frames, the RNG init,
-// render launches, the accumulator / aux / RNG transfers, counters and timing.  The row-tile
-// gather is cpt_capi_gather.cpp, the display path cpt_capi_display.cpp, the diagnostic probes and
-// self-tests cpt_capi_probes.cpp.  The scene half (upload, material slots, walk trees, device
+// render launches, the accumulator / aux / RNG transfers, counters and timing.  The adaptive
+// render is cpt_capi_adaptive.cpp, the row-tile gather cpt_capi_gather.cpp, the display path
+// cpt_capi_display.cpp, the diagnostic probes and self-tests cpt_capi_probes.cpp.  The scene half (upload, material slots, walk trees, device
 // refit) is cpt_scene.cpp; the host BVH builds and the XORWOW tables are cpt_host_bvh.cpp /
 // cpt_host_rng.cpp.
 #include <hip/hip_runtime.h>
@@ -299,8 +299,11 @@ int cpt_write_rng(cpt_ctx* c, const uint32_t* planar6) {
     return CPT_OK;
 }
 
-// The megakernel's parameters for a render of the context's frame (cpt_render, cpt_tile_costs).
-static void fill_params(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32_t flags, cpt::KParams& p) {
+}  // extern "C"
+
+// The megakernel's parameters for a render of the context's frame (cpt_render, cpt_tile_costs,
+// cpt_render_adaptive).
+void cpt::ctx::fill_params(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32_t flags, cpt::KParams& p) {
     std::memset(&p, 0, sizeof(p));
     p.nodes = c->d_nodes;
     p.mats = c->d_mats;
@@ -354,7 +357,7 @@ static void fill_params(cpt_ctx* c, const cpt_camera* cam, int spp, int max_dept
 }
 
 // The 8x8 tiles of the context's frame rows.
-static size_t n_tiles(const cpt_ctx* c) { return (size_t)((c->width + 7) / 8) * ((c->n_rows + 7) / 8); }
+size_t cpt::ctx::n_tiles(const cpt_ctx* c) { return (size_t)((c->width + 7) / 8) * ((c->n_rows + 7) / 8); }
 
 // The one list of the wavefront path's arrays: each is allocated for its view pointer's element
 // type and the view filled from the same call.
@@ -432,7 +435,8 @@ static int previous_order_refresh(cpt_ctx* c, const cpt::KParams& p, hipStream_t
 // per 128 spp against round 5's 4 at one per 512: C4 2182-2198 vs 2065-2072 Mpaths/s (8 passes
 // at one per 256: 2159-2175), C5 N = 8 slowest rank 2101 vs 2388 ms; C2 / C3 unchanged.
 constexpr int PILOT_MAX = 16, PILOT_DIV = 128;
-static int cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStream_t s) {
+int cpt::ctx::cost_pilot_passes(int spp) { return std::min(PILOT_MAX, std::max(1, spp / PILOT_DIV)); }
+int cpt::ctx::cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStream_t s) {
     Frame& f = c->frame;
     int rc;
     if ((rc = f.d_sched.ensure(c, cpt::tile_schedule_scratch_bytes(c->width, c->n_rows))) != CPT_OK) return rc;
@@ -452,7 +456,7 @@ static int cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStream_t
 // N = 8, slowest rank: 309 vs 322 ms in r06, 314-318 vs 322 in r05, 304 vs 325 with
 // this rule; profiles/r06/reh_cons_r06z.log, r06/cert/reh_c4_cons_rule.log,
 // profiles/r05/reh_cons_off_vs_auto.log).
-static int consolidation_slab(cpt_ctx* c, cpt::KParams& p, int spp, uint32_t flags) {
+int cpt::ctx::consolidation_slab(cpt_ctx* c, cpt::KParams& p, int spp, uint32_t flags) {
     const size_t cus = (size_t)c->cus;
     const size_t frame_px = c->npix(), grid_lanes = 1024u * cus;
     const bool cons = (flags & CPT_SCHEDULE_CONSOLIDATE) ||
@@ -465,6 +469,8 @@ static int consolidation_slab(cpt_ctx* c, cpt::KParams& p, int spp, uint32_t fla
     p.resume_cap = cap;
     return CPT_OK;
 }
+
+extern "C" {
 
 int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32_t flags) {
     if (!c || !cam) return CPT_ERR_INVALID_ARG;
@@ -502,7 +508,7 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
         const bool previous = !(flags & CPT_SCHEDULE_COST) && (flags & CPT_SCHEDULE_PREVIOUS) && work;
         if (previous && (rc = previous_order_begin(c, p, s)) != CPT_OK) return rc;
         if (cost) {
-            if ((rc = cost_pilot(c, p, std::min(PILOT_MAX, std::max(1, spp / PILOT_DIV)), s)) != CPT_OK) return rc;
+            if ((rc = cost_pilot(c, p, cost_pilot_passes(spp), s)) != CPT_OK) return rc;
             p.tile_order = f.d_tile_order;
         }
         if ((rc = consolidation_slab(c, p, spp, flags)) != CPT_OK) return rc;

@@ -1,7 +1,8 @@
 // cpt_context.hpp — the C-ABI's context (struct cpt_ctx of include/cpt.h) and the helpers its
 // implementation files share: cpt_capi.cpp (context, frame, RNG, render, accumulator, counters),
-// cpt_capi_gather.cpp (row-tile gather), cpt_capi_display.cpp (display path), cpt_capi_probes.cpp
-// (diagnostic probes, self-tests) and cpt_scene.cpp (scene upload, material slots, walk trees,
+// cpt_capi_adaptive.cpp (adaptive render), cpt_capi_gather.cpp (row-tile gather),
+// cpt_capi_display.cpp (display path), cpt_capi_probes.cpp (diagnostic probes, self-tests) and
+// cpt_scene.cpp (scene upload, material slots, walk trees,
 // device refit).  Host code only.
 #pragma once
 
@@ -55,6 +56,16 @@ struct Frame {
     DevBuf<uint8_t> d_bgra;      // display frame (band rows)
     DevBuf<float4> d_dn_sink;    // k_denoise_strip: where lanes without an output pixel store (DN_SINK_SLOTS)
     int band_y0 = -1, band_y1 = -1;   // display band the buffers hold
+    // adaptive render (cpt_capi_adaptive.cpp; allocated on the frame's first cpt_render_adaptive):
+    // the accumulator before the current round, the per-pixel moments and noise map (planar
+    // [4][npix]: m1, m2, k, rel), a keep flag per position of the active list, the list's two
+    // buffers (each round compacts one into the other) and {new length, pixels rendered}
+    DevBuf<float4> d_ad_snap;
+    DevBuf<float> d_ad_stat;
+    DevBuf<uint32_t> d_ad_keep, d_ad_order[2], d_ad_count;
+    bool ad_done = false;                  // an adaptive render has completed on this frame
+    std::vector<uint32_t> ad_active;       // its rounds: the tiles each one rendered
+    uint64_t ad_passes = 0;                // its pixel passes, all rounds
 };
 
 // ======================================================================================
@@ -161,6 +172,14 @@ int sync_checked(cpt_ctx* c);
 // A device-to-device copy from one of the context's buffers, ordered against the caller's
 // stream without a host wait (cpt_capi.cpp).
 int copy_ordered(cpt_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t caller);
+// What a megakernel launch of the context's frame is made of (cpt_capi.cpp; shared with
+// cpt_capi_adaptive.cpp): the kernel parameters, the frame's 8x8 tiles, the cost schedule's pilot
+// into Frame::d_tile_order and its length for a render of `spp` passes, the consolidation slab.
+void fill_params(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32_t flags, cpt::KParams& p);
+size_t n_tiles(const cpt_ctx* c);
+int cost_pilot_passes(int spp);
+int cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStream_t s);
+int consolidation_slab(cpt_ctx* c, cpt::KParams& p, int spp, uint32_t flags);
 
 // cpt_scene.cpp
 int material_slot(cpt_ctx* c, const cpt_material& m);

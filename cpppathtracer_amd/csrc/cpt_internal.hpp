@@ -70,6 +70,9 @@ struct KParams {
     // (0 = the defaults, 2^26 and 2^22).
     uint32_t dbg;
     int keeper_spin_log2, publish_wait_log2;
+    // Adaptive render (cpt_render_adaptive): only the first n_active entries of tile_order are
+    // dequeued (tiles still noisy); 0 = every tile of the frame, as every other launch passes.
+    uint32_t n_active;
 };
 
 // Device error bits (KParams::error).
@@ -92,6 +95,28 @@ hipError_t launch_tile_order_from_draws(const KParams& p, uint32_t* d_prev, void
                                         uint32_t* order, hipStream_t stream);
 hipError_t launch_tile_schedule(const KParams& p, int passes, void* scratch, size_t scratch_bytes, uint32_t* order,
                                 int max_workgroups, hipStream_t stream);
+
+// Adaptive render (cpt_adaptive.hip, DESIGN.md §Adaptive sampling).  After a round of `batch`
+// passes over the first n_active tiles of `order` (nullptr: tiles 0..n_active-1), launch_tile_noise
+// folds the round's batch mean of every pixel of those tiles into its moments (cpt_adaptive.hpp),
+// copies the accumulator into the snapshot and writes keep[i] for each list position i: 0 when the
+// tile leaves the list (all its pixels converged in an `eligible` round, or the `last` round).
+struct AdaptiveRound {
+    const uint32_t* order;
+    uint32_t n_active;
+    int width, n_rows;
+    const float4* accum;    // [n_rows*width] after the round
+    float4* snap;           // [n_rows*width] before the round; after it on return
+    float* stat;            // planar [4][n_rows*width]: m1, m2, k, rel (the noise map)
+    uint32_t* keep;         // [n_active]
+    float rel_error;
+    int eligible, last;
+};
+hipError_t launch_tile_noise(const AdaptiveRound& a, hipStream_t stream);
+// dst := the kept entries of src (nullptr: 0..n-1) in their order (a stable compaction);
+// out[0] = their number, out[1] = the frame pixels of the n tiles of the input list.
+hipError_t launch_compact_order(const uint32_t* src, const uint32_t* keep, uint32_t n, int width, int n_rows,
+                                uint32_t* dst, uint32_t* out, hipStream_t stream);
 
 // Wavefront path state (cpt_wavefront.hip): SoA float4 arrays indexed by QUEUE SLOT + queues.
 // The carried state is double-buffered: bounce b reads buffer b & 1 at its queue slot and shade

@@ -152,7 +152,8 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
     }
     const int lane = threadIdx.x & 63;
     const size_t npix = (size_t)p.n_rows * p.width;
-    const uint32_t n_work = (uint32_t)(((p.width + 7) >> 3) * ((p.n_rows + 7) >> 3)) * 64u;
+    // (an adaptive render's later rounds dequeue only the first n_active tiles of p.tile_order)
+    const uint32_t n_work = (p.n_active ? p.n_active : (uint32_t)(((p.width + 7) >> 3) * ((p.n_rows + 7) >> 3))) * 64u;
     const uint32_t max_depth = (uint32_t)p.max_depth;
     Counters cnt{};
     uint32_t work_at_take = 0;   // PROBE: the lane's counters when it took its pixel
@@ -658,7 +659,7 @@ static hipError_t launch_mk(const KParams& p, int max_workgroups, hipStream_t st
         if (blocks_per_cu < 1) blocks_per_cu = 1;
     }
     // persistent grid: every resident slot once; lanes pull pixels from p.work
-    const long long tiles = (long long)((p.width + 7) / 8) * ((p.n_rows + 7) / 8);
+    const long long tiles = p.n_active ? (long long)p.n_active : (long long)((p.width + 7) / 8) * ((p.n_rows + 7) / 8);
     // a wave holds p.lanes / p.replicate pixels at once (64 in normal use; fewer: DIAGNOSTIC)
     const int per_wave = std::max(1, p.lanes / std::max(1, p.replicate));
     long long want = (tiles * 64 * ((64 + per_wave - 1) / per_wave) + block - 1) / block;

@@ -114,6 +114,7 @@ hipError_t launch_tile_schedule(const KParams& p0, int passes, void* scratch, si
     p.spp = passes;
     p.tile_cost = s.cost;
     p.tile_order = nullptr;
+    p.n_active = 0;
     p.accumulate = 0;
     e = launch_cost_pilot(p, max_workgroups, stream);
     if (e != hipSuccess) return e;

@@ -175,6 +175,28 @@ class Renderer:
             f |= CPT_SCHEDULE_CONSOLIDATE if consolidate else CPT_SCHEDULE_NO_CONSOLIDATE
         self._check(self._L.cpt_render(self._ctx, _p(c), spp, max_depth, f))
 
+    def render_adaptive(self, cam, min_spp, max_spp, batch, rel_error, max_depth, flags=0):
+        """cpt_render_adaptive: rounds of `batch` passes over the 8x8 tiles whose pixels have not all
+        reached a relative standard error of `rel_error` (none leaves before `min_spp`, all at
+        `max_spp`); every pixel ends bit for bit as a render() of its own pass count.  `flags`: the
+        CPT_* render flags (not the wavefront path, not CPT_SCHEDULE_PREVIOUS).  Synchronous.
+        Returns {"rounds", "active_tiles" (uint32 per round), "passes_done" (pixel passes)}."""
+        c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
+        self._check(self._L.cpt_render_adaptive(self._ctx, _p(c), int(min_spp), int(max_spp), int(batch),
+                                                ctypes.c_float(rel_error), int(max_depth), int(flags)))
+        rounds, passes = ctypes.c_int(0), ctypes.c_uint64(0)
+        active = np.zeros(max(1, int(max_spp) // int(batch)), dtype=np.uint32)
+        self._check(self._L.cpt_adaptive_info(self._ctx, ctypes.byref(rounds), _p(active), active.size,
+                                              ctypes.byref(passes)))
+        return {"rounds": rounds.value, "active_tiles": active[:rounds.value].copy(), "passes_done": int(passes.value)}
+
+    def read_noise(self):
+        """The last render_adaptive's noise map (cpt_read_noise): each pixel's relative standard
+        error as its last round left it, [npix] float32 (+inf with fewer than two batches)."""
+        out = np.zeros(self.npix, dtype=np.float32)
+        self._check(self._L.cpt_read_noise(self._ctx, _p(out), out.size))
+        return out
+
     def tile_costs(self, cam, passes, max_depth, ordered=True):
         """The cost schedule's pilot alone (cpt_tile_costs): the work of each 8x8 tile's heaviest
         pixel (the maximum over the tile's pixels, not their sum) over `passes` passes from the

@@ -23,6 +23,7 @@
 // --out writes the raw accumulator mean as float32 rgb (row-major); --dispatch runs K passes
 // through the asynchronous DispatchRay pipeline (1 spp + denoise + mix per pass, callback on
 // the render thread) and writes the last BGRA8 frame to --bgra.
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -147,6 +148,10 @@ int main(int argc, char** argv) {
     std::string scene = "s4", out, bgra_out, pfm, texture, dump_scene;
     int W = 64, H = 36, spp = 2, depth = 8, dispatch = 0, devices = 1, n_objects = 1000, animate = 0;
     unsigned long long seed = 1234;
+    // --adaptive REL: --spp is the most passes a pixel gets; tiles stop once their pixels'
+    // relative standard error is at most REL (PathTracer::RenderAdaptive)
+    float adaptive = -1.f;
+    int min_spp = 0, batch = 0;
     for (int i = 1; i + 1 < argc; i += 2) {
         std::string k = argv[i], v = argv[i + 1];
         if (k == "--scene") scene = v;
@@ -164,6 +169,9 @@ int main(int argc, char** argv) {
         else if (k == "--devices") devices = std::stoi(v);
         else if (k == "--objects") n_objects = std::stoi(v);
         else if (k == "--animate") animate = std::stoi(v);
+        else if (k == "--adaptive") adaptive = std::stof(v);
+        else if (k == "--min-spp") min_spp = std::stoi(v);
+        else if (k == "--batch") batch = std::stoi(v);
         else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 2; }
     }
 
@@ -239,7 +247,21 @@ int main(int argc, char** argv) {
         return 0;
     }
 
-    if (!tracer.Render(spp, false)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
+    if (adaptive >= 0.f) {
+        // defaults: about 16 rounds (a batch that divides --spp), no tile stops before the second
+        if (batch <= 0)
+            for (batch = std::max(1, spp / 16); spp % batch; --batch) {}
+        if (min_spp <= 0) min_spp = std::min(spp, 2 * batch);
+        int rounds = 0;
+        uint64_t passes = 0;
+        if (!tracer.RenderAdaptive(min_spp, spp, batch, adaptive, &rounds, &passes)) {
+            fprintf(stderr, "RenderAdaptive: %s\n", tracer.LastError().c_str());
+            return 1;
+        }
+        printf("adaptive: rel_error %g, %d..%d spp in batches of %d: %d rounds, passes_done %llu (%.1f%% of %d spp)\n",
+               (double)adaptive, min_spp, spp, batch, rounds, (unsigned long long)passes,
+               100.0 * (double)passes / ((double)W * H * spp), spp);
+    } else if (!tracer.Render(spp, false)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
     for (int f = 1; f <= animate; ++f) {
         const auto t0 = std::chrono::steady_clock::now();
         int moved = 0;

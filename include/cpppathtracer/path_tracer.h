@@ -65,6 +65,15 @@ public:
     void SetOrderedTraversal(bool on) { ordered_walk_ = on; }
     // Synchronous `spp` passes into the radiance accumulator (accumulate=false restarts it).
     bool Render(int spp, bool accumulate = true);
+    // Synchronous adaptive render into a restarted accumulator (cpt_render_adaptive): rounds of
+    // `batch` passes over the 8x8 tiles whose pixels have not all reached a relative standard
+    // error of rel_error; none stops before min_spp, all at max_spp.  Each pixel ends as a
+    // Render of its own pass count would leave it.  Single device only.  rounds / passes_done
+    // (optional): the rounds run and the pixel passes of all of them.
+    bool RenderAdaptive(int min_spp, int max_spp, int batch, float rel_error, int* rounds = nullptr,
+                        uint64_t* passes_done = nullptr);
+    // The last RenderAdaptive's per-pixel relative standard error, float[width*height].
+    bool ReadNoise(float* rel);
     // Per-pixel mean radiance, rgb float[width*height*3] (row-major, y down).
     bool ReadRadiance(std::vector<float>& rgb);
     // Last display frame (denoised running mean), BGRA8[width*height*4].

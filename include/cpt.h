@@ -274,6 +274,38 @@ int cpt_write_aux(cpt_ctx* ctx, const float* normal3, const float* depth);
  * least that).  Synchronous. */
 int cpt_tile_costs(cpt_ctx* ctx, const cpt_camera* cam, int passes, int max_depth, uint32_t flags, uint32_t* out,
                    size_t n_out);
+/* Adaptive render (an addition: the reference gives every pixel the same passes,
+ * path_tracer.cu:124-175).  Rounds of `batch` passes; after a round every 8x8 tile whose pixels
+ * have all converged leaves the list of tiles the next round renders, and so does every tile at
+ * max_spp.  A pixel's estimate is the luminance (0.2126, 0.7152, 0.0722) of each round's batch
+ * mean; it has converged when the standard error of the mean of its k >= 2 batch means is at most
+ * rel_error * max(mean, 1e-3) (a NaN never converges).  No tile leaves before min_spp passes.
+ *
+ * Every pixel's accumulator (rgb sums and count) and RNG state end bit for bit as a cpt_render of
+ * that pixel's own number of passes leaves them: each round is cpt_render's launch of `batch`
+ * passes with `flags` (CPT_TRAVERSAL_*, CPT_RENDER_STATS, CPT_RENDER_AUX, CPT_SCHEDULE_[NO_]
+ * CONSOLIDATE; CPT_SCHEDULE_COST runs its pilot once, before round 1, and the rounds filter that
+ * order).  Without CPT_RENDER_ACCUMULATE round 1 overwrites the accumulator; with it the estimate
+ * starts from the current accumulator (a resumed render starts a new estimate).  Counts are per
+ * pixel, which cpt_gather_rows, cpt_denoise_mix, cpt_read_accum and cpt_write_accum already
+ * expect: they need no change.
+ * Rules (else CPT_ERR_INVALID_ARG): batch >= 1; min_spp and max_spp multiples of batch;
+ * batch <= min_spp <= max_spp; min_spp >= 2 * batch unless min_spp == max_spp; rel_error >= 0.
+ * CPT_ERR_UNSUPPORTED: CPT_PATH_WAVEFRONT, CPT_SCHEDULE_PREVIOUS.  Synchronous: the list's length
+ * is read back after every round. */
+int cpt_render_adaptive(cpt_ctx* ctx, const cpt_camera* cam, int min_spp, int max_spp, int batch, float rel_error,
+                        int max_depth, uint32_t flags);
+/* The last adaptive render since cpt_set_frame (CPT_ERR_STATE if none).  cpt_read_noise: each
+ * pixel's relative standard error as its last round left it (the criterion's left side over its
+ * right side's max(mean, 1e-3); +inf with fewer than two batch means), [n_rows*width], capacity in
+ * floats.  cpt_adaptive_info: the rounds run, the tiles each one rendered (the first `capacity` of
+ * them), and the pixel passes of all rounds; each output may be NULL. */
+int cpt_read_noise(cpt_ctx* ctx, float* rel, size_t capacity);
+int cpt_adaptive_info(cpt_ctx* ctx, int* rounds, uint32_t* active_tiles_per_round, int capacity,
+                      uint64_t* passes_done);
+/* HOST ONLY, no GPU: the criterion on a pixel's moments (m1 = sum of its k batch means, m2 = sum
+ * of their squares) at rel_error t, the function the device runs. */
+int cpt_adaptive_decide_host(float m1, float m2, float k, float t, int* converged, float* rel);
 /* Device-to-device copy of the accumulator (e.g. into an RCCL send buffer), ordered against the
  * caller's HIP stream `caller_stream` (NULL: the null stream) without blocking the host: the
  * context's stream first waits for the work queued on caller_stream so far (a fill of dst, a
