@@ -81,6 +81,13 @@ PROTOTYPES = {
     "cpt_read_noise": (_I, [_P, _P, _SZ]),
     "cpt_adaptive_info": (_I, [_P, _P, _P, _I, _P]),
     "cpt_adaptive_decide_host": (_I, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
+    "cpt_read_moments": (_I, [_P, _P, _SZ]),
+    "cpt_write_moments": (_I, [_P, _P, _SZ]),
+    "cpt_filter_frame": (_I, [_P, _I, ctypes.c_float, _I]),
+    "cpt_read_filtered": (_I, [_P, _P, _P, _SZ]),
+    "cpt_last_filter_ms": (_I, [_P, _P]),
+    "cpt_filter_prepare_host": (_I, [_SZ, _P, _P, _P, _P]),
+    "cpt_filter_level_host": (_I, [_I, _I, _I, _P, _P, _P, ctypes.c_float, _I, _P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1

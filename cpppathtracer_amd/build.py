@@ -16,6 +16,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_megakernel.hip"),
     os.path.join(CSRC, "cpt_schedule.hip"),
     os.path.join(CSRC, "cpt_adaptive.hip"),
+    os.path.join(CSRC, "cpt_filter.hip"),
     os.path.join(CSRC, "cpt_display.hip"),
     os.path.join(CSRC, "cpt_selftest.hip"),
     os.path.join(CSRC, "cpt_kernels.hip"),
@@ -25,6 +26,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_capi_display.cpp"),
     os.path.join(CSRC, "cpt_capi_probes.cpp"),
     os.path.join(CSRC, "cpt_capi_adaptive.cpp"),
+    os.path.join(CSRC, "cpt_capi_filter.cpp"),
     os.path.join(CSRC, "cpt_scene.cpp"),
     os.path.join(CSRC, "cpt_host_bvh.cpp"),
     os.path.join(CSRC, "cpt_host_rng.cpp"),

@@ -637,6 +637,28 @@ bool PathTracer::ReadNoise(float* rel) {
     return true;
 }
 
+bool PathTracer::FilterRadiance(int levels, float sigma_l, int sharpness) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!FrameCtx() || width_ == 0 || frame_) {
+        err_ = "FilterRadiance: RenderAdaptive first";
+        return false;
+    }
+    if (cpt_filter_frame(FrameCtx(), levels, sigma_l, sharpness) != CPT_OK) return Fail("cpt_filter_frame");
+    return true;
+}
+
+bool PathTracer::ReadFiltered(std::vector<float>& rgb) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!FrameCtx() || width_ == 0 || frame_) {
+        err_ = "ReadFiltered: FilterRadiance first";
+        return false;
+    }
+    rgb.resize((size_t)width_ * height_ * 3);
+    if (cpt_read_filtered(FrameCtx(), rgb.data(), nullptr, (size_t)width_ * height_) != CPT_OK)
+        return Fail("cpt_read_filtered");
+    return true;
+}
+
 bool PathTracer::ReadRadiance(std::vector<float>& rgb) {
     std::lock_guard<std::mutex> lk(mu_);
     if (!FrameCtx() || width_ == 0) {
@@ -661,18 +683,29 @@ bool PathTracer::ReadFrameBGRA(std::vector<uint8_t>& bgra) {
     return !bgra.empty();
 }
 
+static bool write_pfm(const std::string& path, const std::vector<float>& rgb, int width, int height) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) return false;
+    f << "PF\n" << width << " " << height << "\n-1.0\n";
+    for (int y = height - 1; y >= 0; --y)   // PFM rows are bottom-to-top
+        f.write(reinterpret_cast<const char*>(&rgb[(size_t)y * width * 3]), (std::streamsize)width * 3 * sizeof(float));
+    return (bool)f;
+}
+
 bool PathTracer::SaveRadiancePFM(const std::string& path) {
     std::vector<float> rgb;
     if (!ReadRadiance(rgb)) return false;
-    std::ofstream f(path, std::ios::binary);
-    if (!f) {
-        err_ = "SaveRadiancePFM: cannot open " + path;
-        return false;
-    }
-    f << "PF\n" << width_ << " " << height_ << "\n-1.0\n";
-    for (int y = height_ - 1; y >= 0; --y)   // PFM rows are bottom-to-top
-        f.write(reinterpret_cast<const char*>(&rgb[(size_t)y * width_ * 3]), (std::streamsize)width_ * 3 * sizeof(float));
-    return (bool)f;
+    if (write_pfm(path, rgb, width_, height_)) return true;
+    err_ = "SaveRadiancePFM: cannot write " + path;
+    return false;
+}
+
+bool PathTracer::SaveFilteredPFM(const std::string& path) {
+    std::vector<float> rgb;
+    if (!ReadFiltered(rgb)) return false;
+    if (write_pfm(path, rgb, width_, height_)) return true;
+    err_ = "SaveFilteredPFM: cannot write " + path;
+    return false;
 }
 
 // Counters summed over the tiles (the render flags do not ask for CPT_RENDER_STATS, so these

@@ -140,7 +140,7 @@ int cpt_create(int device, cpt_ctx** out) {
     if (e == hipSuccess) e = hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device);
     c->cus = std::max(c->cus, 1);
     if (e == hipSuccess) e = c->own_stream.create(hipStreamNonBlocking);
-    for (DevEvent* ev : {&c->ev_start, &c->ev_stop, &c->ev_main, &c->ev_dn0, &c->ev_dn1})
+    for (DevEvent* ev : {&c->ev_start, &c->ev_stop, &c->ev_main, &c->ev_dn0, &c->ev_dn1, &c->ev_flt0, &c->ev_flt1})
         if (e == hipSuccess) e = ev->create();
     for (DevEvent* ev : {&c->ev_ready, &c->ev_gathered, &c->ev_caller, &c->ev_copied})
         if (e == hipSuccess) e = ev->create(hipEventDisableTiming);

@@ -1,0 +1,148 @@
+// cpt_capi_filter.cpp — the C-ABI's variance-guided a-trous filter of an adaptive render's final
+// frame (include/cpt.h): cpt_filter_frame and its read-outs, the moments'
+// checkpoint pair, and the host-only hooks on the filter's arithmetic.  The kernels are
+// cpt_filter.hip's; the arithmetic is cpt_filter.hpp's on both sides.
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "cpt_context.hpp"
+#include "cpt_filter.hpp"
+
+using namespace cpt::ctx;
+namespace flt = cpt::filter;
+
+namespace {
+
+bool args_ok(float sigma_l, int sharpness_log2) {
+    return flt::finite(sigma_l) && sigma_l >= 0.f && sharpness_log2 >= 0 && sharpness_log2 <= flt::MAX_SHARPNESS_LOG2;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cpt_filter_frame(cpt_ctx* c, int levels, float sigma_l, int normal_sharpness_log2) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    if (levels < 0 || levels > flt::MAX_LEVELS || !args_ok(sigma_l, normal_sharpness_log2))
+        return fail(c, CPT_ERR_INVALID_ARG,
+                    "cpt_filter_frame: levels %d (0..8), sigma_l %g (finite, >= 0), normal_sharpness_log2 %d (0..10)", levels,
+                    (double)sigma_l, normal_sharpness_log2);
+    Frame& f = c->frame;
+    if (!f.set || c->n_rows != c->height) return fail(c, CPT_ERR_STATE, "cpt_filter_frame: needs a full frame");
+    for (int y = 0; y < c->height; ++y)
+        if (c->rows_h[y] != y) return fail(c, CPT_ERR_STATE, "cpt_filter_frame: needs rows 0..height-1 in order");
+    const size_t npix = c->npix();
+    if (!f.ad_done || f.d_ad_stat.capacity() < 4 * npix)
+        return fail(c, CPT_ERR_STATE, "cpt_filter_frame: no moments (cpt_render_adaptive or cpt_write_moments first)");
+    if (f.d_normal.capacity() < 3 * npix)
+        return fail(c, CPT_ERR_STATE, "cpt_filter_frame: no normals (render with CPT_RENDER_AUX or cpt_write_aux first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = f.d_flt[0].ensure(c, npix)) != CPT_OK || (rc = f.d_flt[1].ensure(c, npix)) != CPT_OK ||
+        (rc = f.d_flt_ok.ensure(c, npix)) != CPT_OK)
+        return rc;
+    f.flt_result = -1;
+    hipStream_t s = c->stream();
+    HIP_TRY(c, hipEventRecord(c->ev_flt0, s));
+    HIP_TRY(c, cpt::launch_filter_prepare(f.d_accum, f.d_ad_stat, npix, f.d_flt[0], f.d_flt_ok, s));
+    for (int l = 0; l < levels; ++l)
+        HIP_TRY(c, cpt::launch_filter_level(f.d_flt[l & 1], f.d_normal, f.d_flt_ok, f.d_flt[(l + 1) & 1], c->width, c->height,
+                                           1 << l, sigma_l * sigma_l, normal_sharpness_log2, s));
+    HIP_TRY(c, hipEventRecord(c->ev_flt1, s));
+    c->have_flt_timing = true;
+    f.flt_result = levels & 1;
+    return CPT_OK;
+}
+
+int cpt_read_filtered(cpt_ctx* c, float* rgb, float* variance, size_t capacity_pixels) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    const Frame& f = c->frame;
+    if (!f.set || f.flt_result < 0) return fail(c, CPT_ERR_STATE, "cpt_read_filtered: cpt_filter_frame first");
+    const size_t n = c->npix();
+    if (capacity_pixels < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_filtered: %zu < %zu pixels", capacity_pixels, n);
+    if (int rc = sync_checked(c)) return rc;
+    std::vector<float> plane(4 * n);
+    HIP_TRY(c, hipMemcpy(plane.data(), f.d_flt[f.flt_result], n * sizeof(float4), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        if (rgb) {
+            rgb[3 * i] = plane[4 * i];
+            rgb[3 * i + 1] = plane[4 * i + 1];
+            rgb[3 * i + 2] = plane[4 * i + 2];
+        }
+        if (variance) variance[i] = plane[4 * i + 3];
+    }
+    return CPT_OK;
+}
+
+int cpt_last_filter_ms(cpt_ctx* c, float* ms) {
+    if (!c || !ms) return CPT_ERR_INVALID_ARG;
+    if (!c->have_flt_timing) return fail(c, CPT_ERR_STATE, "cpt_last_filter_ms: no cpt_filter_frame yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->ev_flt1));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->ev_flt0, c->ev_flt1));
+    return CPT_OK;
+}
+
+int cpt_read_moments(cpt_ctx* c, float* planar4, size_t capacity) {
+    if (!c || !planar4) return CPT_ERR_INVALID_ARG;
+    const Frame& f = c->frame;
+    if (!f.set || !f.ad_done) return fail(c, CPT_ERR_STATE, "cpt_read_moments: cpt_render_adaptive or cpt_write_moments first");
+    const size_t n = 4 * c->npix();
+    if (capacity < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_moments: %zu < %zu floats", capacity, n);
+    if (int rc = sync_checked(c)) return rc;
+    if (n) HIP_TRY(c, hipMemcpy(planar4, f.d_ad_stat, n * sizeof(float), hipMemcpyDeviceToHost));
+    return CPT_OK;
+}
+
+int cpt_write_moments(cpt_ctx* c, const float* planar4, size_t count) {
+    if (!c || !planar4) return CPT_ERR_INVALID_ARG;
+    Frame& f = c->frame;
+    if (!f.set) return fail(c, CPT_ERR_STATE, "cpt_write_moments: no frame");
+    const size_t n = 4 * c->npix();
+    if (count < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_write_moments: %zu < %zu floats", count, n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    if (int rc = f.d_ad_stat.ensure(c, n)) return rc;
+    if (n) HIP_TRY(c, hipMemcpy(f.d_ad_stat, planar4, n * sizeof(float), hipMemcpyHostToDevice));
+    // an adaptive result that no round of this context produced: an empty round record
+    f.ad_active.clear();
+    f.ad_passes = 0;
+    f.ad_done = true;
+    return CPT_OK;
+}
+
+int cpt_filter_prepare_host(size_t npix, const float* accum_rgba, const float* moments_planar4, float* out_rgbv,
+                            uint8_t* out_valid) {
+    if (!accum_rgba || !moments_planar4 || !out_rgbv || !out_valid) return CPT_ERR_INVALID_ARG;
+    for (size_t i = 0; i < npix; ++i) {
+        flt::Px c;
+        const float* S = accum_rgba + 4 * i;
+        out_valid[i] = flt::prepare(S[0], S[1], S[2], S[3], moments_planar4[i], moments_planar4[npix + i],
+                                    moments_planar4[2 * npix + i], c)
+                           ? 1
+                           : 0;
+        out_rgbv[4 * i] = c.r;
+        out_rgbv[4 * i + 1] = c.g;
+        out_rgbv[4 * i + 2] = c.b;
+        out_rgbv[4 * i + 3] = c.v;
+    }
+    return CPT_OK;
+}
+
+int cpt_filter_level_host(int width, int height, int step, const float* in_rgbv, const float* normal3, const uint8_t* valid,
+                          float sigma_l, int normal_sharpness_log2, float* out_rgbv) {
+    if (width <= 0 || height <= 0 || step < 1 || step > (1 << (flt::MAX_LEVELS - 1)) || !in_rgbv || !normal3 || !valid ||
+        !out_rgbv || in_rgbv == out_rgbv || !args_ok(sigma_l, normal_sharpness_log2))
+        return CPT_ERR_INVALID_ARG;
+    const flt::PlaneSrc src{reinterpret_cast<const flt::Px*>(in_rgbv), normal3, valid, width};
+    flt::Px* out = reinterpret_cast<flt::Px*>(out_rgbv);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x)
+            out[(size_t)y * width + x] = src.valid(x, y) ? flt::level_pixel(src, x, y, width, height, step, sigma_l * sigma_l,
+                                                                            normal_sharpness_log2)
+                                                         : src.px(x, y);
+    return CPT_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // cpt_context.hpp — the C-ABI's context (struct cpt_ctx of include/cpt.h) and the helpers its
 // implementation files share: cpt_capi.cpp (context, frame, RNG, render, accumulator, counters),
-// cpt_capi_adaptive.cpp (adaptive render), cpt_capi_gather.cpp (row-tile gather),
+// cpt_capi_adaptive.cpp (adaptive render), cpt_capi_filter.cpp (a-trous filter), cpt_capi_gather.cpp (row-tile gather),
 // cpt_capi_display.cpp (display path), cpt_capi_probes.cpp (diagnostic probes, self-tests) and
 // cpt_scene.cpp (scene upload, material slots, walk trees,
 // device refit).  Host code only.
@@ -66,6 +66,12 @@ struct Frame {
     bool ad_done = false;                  // an adaptive render has completed on this frame
     std::vector<uint32_t> ad_active;       // its rounds: the tiles each one rendered
     uint64_t ad_passes = 0;                // its pixel passes, all rounds
+    // a-trous filter (cpt_capi_filter.cpp; allocated on the frame's first cpt_filter_frame): the two
+    // planes the levels ping-pong between (rgb + variance of the mean), each pixel's validity, and
+    // the plane that holds the last call's result (-1: no call yet)
+    DevBuf<float4> d_flt[2];
+    DevBuf<uint8_t> d_flt_ok;
+    int flt_result = -1;
 };
 
 // ======================================================================================
@@ -82,6 +88,8 @@ struct cpt_ctx {
     bool have_timing = false;
     DevEvent ev_dn0, ev_dn1;   // around the last display kernel (k_denoise_rows)
     bool have_dn_timing = false;
+    DevEvent ev_flt0, ev_flt1;   // around the last cpt_filter_frame's launches
+    bool have_flt_timing = false;
     std::string err;
 
     // scene

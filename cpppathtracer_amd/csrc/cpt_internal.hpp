@@ -118,6 +118,15 @@ hipError_t launch_tile_noise(const AdaptiveRound& a, hipStream_t stream);
 hipError_t launch_compact_order(const uint32_t* src, const uint32_t* keep, uint32_t n, int width, int n_rows,
                                 uint32_t* dst, uint32_t* out, hipStream_t stream);
 
+// The a-trous filter of cpt_filter_frame (cpt_filter.hip).  launch_filter_prepare:
+// plane[i] = (mean rgb, variance of the mean) and ok[i] = validity of pixel i, from the accumulator
+// and the adaptive moments `stat` (planar [4][npix]).  launch_filter_level: one level at `step`
+// from plane `in` into plane `out` (sig2 = sigma_l squared); normal3 and ok are only read.
+hipError_t launch_filter_prepare(const float4* accum, const float* stat, size_t npix, float4* plane, uint8_t* ok,
+                                 hipStream_t stream);
+hipError_t launch_filter_level(const float4* in, const float* normal3, const uint8_t* ok, float4* out, int width, int height,
+                               int step, float sig2, int sharpness_log2, hipStream_t stream);
+
 // Wavefront path state (cpt_wavefront.hip): SoA float4 arrays indexed by QUEUE SLOT + queues.
 // The carried state is double-buffered: bounce b reads buffer b & 1 at its queue slot and shade
 // writes each surviving path into buffer (b + 1) & 1 at the slot the compaction gave it, so

@@ -47,5 +47,12 @@ constexpr int TAKE_TAPER = 4;
 // rank (profiles/r05/reh_cons_retire_threshold.log): 128 / 192 / 384 2574-2582 ms against 2521 /
 // 2551 at 256.
 constexpr int CONS_RETIRE_PER_LEVEL = 256;
+// The a-trous filter (cpt_filter.hip k_filter_level) stages a block's taps in LDS for the levels of
+// step <= this (0: every level reads its taps from global memory; at most 2: from step 4 on the
+// halo outgrows the 64 x 4 block).  DESIGN.md §19 has the measurements.
+#ifndef CPT_FILTER_LDS_MAX_STEP
+#define CPT_FILTER_LDS_MAX_STEP 2
+#endif
+constexpr int FILTER_LDS_MAX_STEP = CPT_FILTER_LDS_MAX_STEP;
 
 }  // namespace cpt

@@ -197,6 +197,44 @@ class Renderer:
         self._check(self._L.cpt_read_noise(self._ctx, _p(out), out.size))
         return out
 
+    def read_moments(self):
+        """The adaptive render's per-pixel moments (cpt_read_moments): [4, npix] float32, the sum
+        m1 of each pixel's k batch means' luminance, the sum m2 of their squares, k, and the noise
+        map."""
+        out = np.zeros((4, self.npix), dtype=np.float32)
+        self._check(self._L.cpt_read_moments(self._ctx, _p(out), out.size))
+        return out
+
+    def write_moments(self, planar4):
+        """Restore the moments ([4, npix] float32) from a host copy (cpt_write_moments): with
+        write_accum, write_rng and write_aux, the checkpoint of an adaptive session."""
+        a = np.ascontiguousarray(planar4, dtype=np.float32)
+        if a.shape != (4, self.npix):
+            raise ValueError(f"write_moments: expected shape (4, {self.npix}), got {a.shape}")
+        self._check(self._L.cpt_write_moments(self._ctx, _p(a), a.size))
+
+    def filter_frame(self, levels=5, sigma_l=1.0, normal_sharpness_log2=7):
+        """cpt_filter_frame: the variance-guided a-trous filter of the frame an adaptive render left
+        (needs a full frame, moments, and normals from CPT_RENDER_AUX or write_aux).  `levels`
+        5x5 B3-spline iterations at step 1, 2, 4, ..., edge-stopped by the first-hit normals
+        (sharper with a larger normal_sharpness_log2) and by luminance differences of more than
+        about sigma_l standard errors.  Asynchronous; read_filtered waits."""
+        self._check(self._L.cpt_filter_frame(self._ctx, int(levels), ctypes.c_float(sigma_l), int(normal_sharpness_log2)))
+
+    def read_filtered(self):
+        """The last filter_frame's result (cpt_read_filtered): (rgb [npix, 3], variance of the
+        filtered mean [npix]) float32."""
+        rgb = np.zeros((self.npix, 3), dtype=np.float32)
+        var = np.zeros(self.npix, dtype=np.float32)
+        self._check(self._L.cpt_read_filtered(self._ctx, _p(rgb), _p(var), self.npix))
+        return rgb, var
+
+    def last_filter_ms(self) -> float:
+        """Device time of the last filter_frame, all its launches (HIP events); waits for it."""
+        ms = ctypes.c_float(0)
+        self._check(self._L.cpt_last_filter_ms(self._ctx, ctypes.byref(ms)))
+        return float(ms.value)
+
     def tile_costs(self, cam, passes, max_depth, ordered=True):
         """The cost schedule's pilot alone (cpt_tile_costs): the work of each 8x8 tile's heaviest
         pixel (the maximum over the tile's pixels, not their sum) over `passes` passes from the

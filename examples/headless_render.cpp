@@ -152,8 +152,19 @@ int main(int argc, char** argv) {
     // relative standard error is at most REL (PathTracer::RenderAdaptive)
     float adaptive = -1.f;
     int min_spp = 0, batch = 0;
-    for (int i = 1; i + 1 < argc; i += 2) {
-        std::string k = argv[i], v = argv[i + 1];
+    // --filter [LEVELS] (with --adaptive): the variance-guided a-trous filter of the adaptive frame
+    // (PathTracer::FilterRadiance, 5 levels by default); --pfm then gets the filtered image
+    int filter_levels = -1;
+    for (int i = 1; i < argc; i += 2) {
+        std::string k = argv[i];
+        if (k == "--filter") {
+            const bool has_value = i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0;
+            filter_levels = has_value ? std::stoi(argv[i + 1]) : 5;
+            if (!has_value) --i;
+            continue;
+        }
+        if (i + 1 >= argc) break;
+        std::string v = argv[i + 1];
         if (k == "--scene") scene = v;
         else if (k == "--width") W = std::stoi(v);
         else if (k == "--height") H = std::stoi(v);
@@ -261,6 +272,10 @@ int main(int argc, char** argv) {
         printf("adaptive: rel_error %g, %d..%d spp in batches of %d: %d rounds, passes_done %llu (%.1f%% of %d spp)\n",
                (double)adaptive, min_spp, spp, batch, rounds, (unsigned long long)passes,
                100.0 * (double)passes / ((double)W * H * spp), spp);
+        if (filter_levels >= 0) {
+            if (!tracer.FilterRadiance(filter_levels)) { fprintf(stderr, "FilterRadiance: %s\n", tracer.LastError().c_str()); return 1; }
+            printf("filtered: %d levels\n", filter_levels);
+        }
     } else if (!tracer.Render(spp, false)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
     for (int f = 1; f <= animate; ++f) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -284,6 +299,7 @@ int main(int argc, char** argv) {
         std::ofstream f(out, std::ios::binary);
         f.write(reinterpret_cast<const char*>(rgb.data()), (std::streamsize)(rgb.size() * sizeof(float)));
     }
-    if (!pfm.empty() && !tracer.SaveRadiancePFM(pfm)) { fprintf(stderr, "%s\n", tracer.LastError().c_str()); return 1; }
+    const bool filtered = adaptive >= 0.f && filter_levels >= 0 && animate == 0;
+    if (!pfm.empty() && !(filtered ? tracer.SaveFilteredPFM(pfm) : tracer.SaveRadiancePFM(pfm))) { fprintf(stderr, "%s\n", tracer.LastError().c_str()); return 1; }
     return 0;
 }

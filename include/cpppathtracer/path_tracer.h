@@ -10,8 +10,8 @@
 //   SetCamera / GetCamera
 // Additions the headless configs need (the reference has no setters for these):
 //   SetMaxRecursionDepth, SetSeed, SetDevice, SetDevices (row tiling over several GPUs),
-//   SetEnvTexture, Render(spp) (synchronous), ReadRadiance, ReadFrameBGRA, SaveRadiancePFM,
-//   GetStats, Stop.
+//   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance,
+//   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, GetStats, Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -74,6 +74,14 @@ public:
                         uint64_t* passes_done = nullptr);
     // The last RenderAdaptive's per-pixel relative standard error, float[width*height].
     bool ReadNoise(float* rel);
+    // Variance-guided a-trous filter of the last RenderAdaptive's frame (cpt_filter_frame):
+    // `levels` 5x5 iterations (0..8) at step 1, 2, 4, ..., edge-stopped by the first-hit normals
+    // (max(N.N', 0) squared `sharpness` times, 0..10) and by luminance differences of more than
+    // about sigma_l standard errors of the pixel's mean.  The radiance accumulator is not
+    // changed; ReadFiltered / SaveFilteredPFM read the result (rgb float[width*height*3]).
+    bool FilterRadiance(int levels = 5, float sigma_l = 1.0f, int sharpness = 7);
+    bool ReadFiltered(std::vector<float>& rgb);
+    bool SaveFilteredPFM(const std::string& path);
     // Per-pixel mean radiance, rgb float[width*height*3] (row-major, y down).
     bool ReadRadiance(std::vector<float>& rgb);
     // Last display frame (denoised running mean), BGRA8[width*height*4].

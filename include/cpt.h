@@ -306,6 +306,51 @@ int cpt_adaptive_info(cpt_ctx* ctx, int* rounds, uint32_t* active_tiles_per_roun
 /* HOST ONLY, no GPU: the criterion on a pixel's moments (m1 = sum of its k batch means, m2 = sum
  * of their squares) at rel_error t, the function the device runs. */
 int cpt_adaptive_decide_host(float m1, float m2, float k, float t, int* converged, float* rel);
+/* The adaptive render's per-pixel moments, planar [4][n_rows*width]: m1 (the sum of the pixel's k
+ * batch means' luminance), m2 (the sum of their squares), k, rel (cpt_read_noise's plane);
+ * capacity / count in floats, at least 4 * n_rows * width (else CPT_ERR_INVALID_ARG, nothing
+ * written).  With cpt_read/write_accum, _rng and _aux they complete the checkpoint of an adaptive
+ * session: cpt_write_moments marks the frame as holding an adaptive result with an empty round
+ * record (cpt_adaptive_info: 0 rounds, 0 passes), so cpt_read_noise and cpt_filter_frame work on a
+ * restored frame.  cpt_read_moments before either: CPT_ERR_STATE.  The moments of a render resumed
+ * with CPT_RENDER_ACCUMULATE describe only the passes of that call, not the accumulator's earlier
+ * ones; a plain cpt_render leaves them as they were. */
+int cpt_read_moments(cpt_ctx* ctx, float* planar4, size_t capacity);
+int cpt_write_moments(cpt_ctx* ctx, const float* planar4, size_t count);
+
+/* Variance-guided a-trous filter of the frame an adaptive render left (an addition: the
+ * reference's only filter is the per-pass Denoising + Mix, path_tracer.cu:177-254):
+ * `levels` iterations (0..8) of a 5x5 B3-spline stencil at step 1, 2, 4, ... over the mean image
+ * accumulator rgb / count, each tap weighted by the first-hit normals' agreement (max(Np.Nq, 0)
+ * squared normal_sharpness_log2 times, 0..10) and by den / (den + d^2), d the luminance
+ * difference and den = sigma_l^2 x the 3x3-prefiltered variance of the mean + 1e-10 (sigma_l
+ * finite and >= 0); the variance of the mean (from the moments) is propagated through every level.
+ * A pixel without a pass, with fewer than two batch means or with a value that is not finite is
+ * left as it is and is no tap of another pixel.  Defaults in the wrappers: 5 levels, sigma_l 1,
+ * sharpness 7 (the measurements behind sigma_l).  Bad arguments: CPT_ERR_INVALID_ARG.
+ * Needs (else CPT_ERR_STATE) a full frame (rows == NULL, as cpt_denoise_mix), moments
+ * (cpt_render_adaptive or cpt_write_moments) and first-hit normals (CPT_RENDER_AUX or
+ * cpt_write_aux).  A row-tiled render filters on each tile's own context: cpt_gather_rows does not
+ * carry moments.  Reads the accumulator, the moments and the normals and writes none of them (nor
+ * the RNG); the result lives in buffers of its own until the next call or cpt_set_frame.
+ * Asynchronous, on the context's stream. */
+int cpt_filter_frame(cpt_ctx* ctx, int levels, float sigma_l, int normal_sharpness_log2);
+/* The last cpt_filter_frame's result (CPT_ERR_STATE if none since cpt_set_frame): rgb
+ * [n_rows*width][3] and the variance of the filtered mean [n_rows*width]; either may be NULL.
+ * capacity_pixels below n_rows*width: CPT_ERR_INVALID_ARG, nothing written.  Waits. */
+int cpt_read_filtered(cpt_ctx* ctx, float* rgb, float* variance, size_t capacity_pixels);
+/* Device time of the last cpt_filter_frame, all its launches (HIP events on the context's stream);
+ * waits for it. */
+int cpt_last_filter_ms(cpt_ctx* ctx, float* ms);
+/* HOST ONLY, no GPU: the functions the device runs.  cpt_filter_prepare_host: level 0 of npix
+ * pixels from an accumulator [npix][4] and moments [4][npix] into out_rgbv [npix][4] (mean rgb,
+ * variance of the mean) and out_valid [npix] (1 or 0).  cpt_filter_level_host: one level at
+ * `step` (1..128) of a width x height plane in_rgbv with normals normal3 [npix][3] and validity
+ * `valid` into out_rgbv (not in place). */
+int cpt_filter_prepare_host(size_t npix, const float* accum_rgba, const float* moments_planar4, float* out_rgbv,
+                            uint8_t* out_valid);
+int cpt_filter_level_host(int width, int height, int step, const float* in_rgbv, const float* normal3, const uint8_t* valid,
+                          float sigma_l, int normal_sharpness_log2, float* out_rgbv);
 /* Device-to-device copy of the accumulator (e.g. into an RCCL send buffer), ordered against the
  * caller's HIP stream `caller_stream` (NULL: the null stream) without blocking the host: the
  * context's stream first waits for the work queued on caller_stream so far (a fill of dst, a
