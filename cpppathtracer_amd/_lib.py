@@ -78,6 +78,8 @@ PROTOTYPES = {
     "cpt_set_debug_consolidation": (_I, [_P, _U32, _I, _I]),
     "cpt_set_debug_grid": (_I, [_P, _I, _I]),
     "cpt_render_adaptive": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _U32]),
+    "cpt_adaptive_begin": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _U32]),
+    "cpt_adaptive_step": (_I, [_P, _P]),
     "cpt_read_noise": (_I, [_P, _P, _SZ]),
     "cpt_adaptive_info": (_I, [_P, _P, _P, _I, _P]),
     "cpt_adaptive_decide_host": (_I, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),

@@ -603,6 +603,60 @@ bool PathTracer::Render(int spp, bool accumulate) {
     return RenderPass(cma, spp, accumulate);
 }
 
+// The adaptive render over row tiles: every tile's first round is queued, then this thread goes
+// round the unfinished tiles, each step reading one tile's round and queueing its next, so every
+// device has a round queued while the host waits on another.  The tiles are whole 8-row blocks, so
+// each tile's 8x8 tiles are the monolithic frame's and stop at the monolithic frame's rounds.
+bool PathTracer::RenderAdaptiveTiles(MotionalCamera& cam, int min_spp, int max_spp, int batch, float rel_error,
+                                     uint32_t flags, int* rounds, uint64_t* passes_done) {
+    const size_t n = tiles_.size();
+    std::vector<char> pending(n, 0);
+    // a failure leaves no tile pending: the others' rounds are run to their end (a failed step
+    // ends its own)
+    auto fail_all = [&](const char* what, cpt_ctx* ctx) {
+        Fail(what, ctx);
+        for (size_t i = 0; i < n; ++i)
+            for (int active = 1; pending[i] && active > 0;)
+                if (cpt_adaptive_step(tiles_[i].ctx, &active) != CPT_OK) break;
+        return false;
+    };
+    for (size_t i = 0; i < n; ++i) {
+        if (cpt_adaptive_begin(tiles_[i].ctx, reinterpret_cast<const cpt_camera*>(&cam), min_spp, max_spp, batch, rel_error,
+                               (int)max_recursion_depth_, flags) != CPT_OK)
+            return fail_all("cpt_adaptive_begin", tiles_[i].ctx);
+        pending[i] = 1;
+    }
+    for (size_t left = n; left > 0;)
+        for (size_t i = 0; i < n; ++i) {
+            if (!pending[i]) continue;
+            int active = 0;
+            if (cpt_adaptive_step(tiles_[i].ctx, &active) != CPT_OK) {
+                pending[i] = 0;
+                return fail_all("cpt_adaptive_step", tiles_[i].ctx);
+            }
+            if (active == 0) {
+                pending[i] = 0;
+                --left;
+            }
+        }
+    for (Tile& t : tiles_)
+        if (cpt_gather_rows(frame_, t.ctx) != CPT_OK) return Fail("cpt_gather_rows", frame_);
+    if (cpt_synchronize(frame_) != CPT_OK) return Fail("cpt_synchronize", frame_);
+    int most = 0;
+    uint64_t sum = 0;
+    for (Tile& t : tiles_) {
+        if (cpt_synchronize(t.ctx) != CPT_OK) return Fail("cpt_synchronize", t.ctx);
+        int r = 0;
+        uint64_t p = 0;
+        if (cpt_adaptive_info(t.ctx, &r, nullptr, 0, &p) != CPT_OK) return Fail("cpt_adaptive_info", t.ctx);
+        most = std::max(most, r);
+        sum += p;
+    }
+    if (rounds) *rounds = most;
+    if (passes_done) *passes_done = sum;
+    return true;
+}
+
 bool PathTracer::RenderAdaptive(int min_spp, int max_spp, int batch, float rel_error, int* rounds,
                                 uint64_t* passes_done) {
     if (!camera_) {
@@ -613,13 +667,10 @@ bool PathTracer::RenderAdaptive(int min_spp, int max_spp, int batch, float rel_e
     MotionalCamera cma = camera_->GetCopy();
     std::lock_guard<std::mutex> lk(mu_);
     if (!SyncScene() || !EnsureFrame(cma)) return false;
-    if (frame_) {   // row tiles stop independently; their rounds are not stitched
-        err_ = "RenderAdaptive: one device only";
-        return false;
-    }
-    cpt_ctx* ctx = tiles_[0].ctx;
     const uint32_t flags = CPT_RENDER_AUX | (ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) |
                            (max_spp >= 64 ? CPT_SCHEDULE_COST : 0u);
+    if (frame_) return RenderAdaptiveTiles(cma, min_spp, max_spp, batch, rel_error, flags, rounds, passes_done);
+    cpt_ctx* ctx = tiles_[0].ctx;
     if (cpt_render_adaptive(ctx, reinterpret_cast<const cpt_camera*>(&cma), min_spp, max_spp, batch, rel_error,
                             (int)max_recursion_depth_, flags) != CPT_OK)
         return Fail("cpt_render_adaptive", ctx);
@@ -629,7 +680,7 @@ bool PathTracer::RenderAdaptive(int min_spp, int max_spp, int batch, float rel_e
 
 bool PathTracer::ReadNoise(float* rel) {
     std::lock_guard<std::mutex> lk(mu_);
-    if (!FrameCtx() || width_ == 0 || frame_) {
+    if (!FrameCtx() || width_ == 0) {
         err_ = "ReadNoise: RenderAdaptive first";
         return false;
     }
@@ -639,7 +690,7 @@ bool PathTracer::ReadNoise(float* rel) {
 
 bool PathTracer::FilterRadiance(int levels, float sigma_l, int sharpness) {
     std::lock_guard<std::mutex> lk(mu_);
-    if (!FrameCtx() || width_ == 0 || frame_) {
+    if (!FrameCtx() || width_ == 0) {
         err_ = "FilterRadiance: RenderAdaptive first";
         return false;
     }
@@ -649,7 +700,7 @@ bool PathTracer::FilterRadiance(int levels, float sigma_l, int sharpness) {
 
 bool PathTracer::ReadFiltered(std::vector<float>& rgb) {
     std::lock_guard<std::mutex> lk(mu_);
-    if (!FrameCtx() || width_ == 0 || frame_) {
+    if (!FrameCtx() || width_ == 0) {
         err_ = "ReadFiltered: FilterRadiance first";
         return false;
     }

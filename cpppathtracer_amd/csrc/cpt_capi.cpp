@@ -142,8 +142,9 @@ int cpt_create(int device, cpt_ctx** out) {
     if (e == hipSuccess) e = c->own_stream.create(hipStreamNonBlocking);
     for (DevEvent* ev : {&c->ev_start, &c->ev_stop, &c->ev_main, &c->ev_dn0, &c->ev_dn1, &c->ev_flt0, &c->ev_flt1})
         if (e == hipSuccess) e = ev->create();
-    for (DevEvent* ev : {&c->ev_ready, &c->ev_gathered, &c->ev_caller, &c->ev_copied})
+    for (DevEvent* ev : {&c->ev_ready, &c->ev_gathered, &c->ev_caller, &c->ev_copied, &c->ev_round})
         if (e == hipSuccess) e = ev->create(hipEventDisableTiming);
+    if (e == hipSuccess) e = c->h_ad_words.alloc(4);
     if (e == hipSuccess) e = c->d_stats.alloc(128);   // [64..128) execdiag
     if (e == hipSuccess) e = c->d_work.alloc(16);     // 64 B: [0] dequeue counter, [4] error word
     if (e == hipSuccess) e = hipMemset(c->d_work, 0, 64);
@@ -219,6 +220,7 @@ int cpt_set_frame(cpt_ctx* c, int width, int height, const int32_t* rows, int n_
     // the megakernel keeps a lane's pixel as 16-bit x / y and a 32-bit index
     if (width > 65535 || height > 65535)
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_set_frame: %dx%d exceeds 65535 pixels per axis", width, height);
+    CPT_REFUSE_PENDING(c, "cpt_set_frame");
     std::vector<int32_t> r;
     if (rows) {
         if (n_rows < 0) return fail(c, CPT_ERR_INVALID_ARG, "cpt_set_frame: n_rows %d", n_rows);
@@ -476,6 +478,7 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
     if (!c || !cam) return CPT_ERR_INVALID_ARG;
     if (spp < 0 || max_depth < 0 || max_depth > (int)cpt::MAX_RECURSION_DEPTH_SET)
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_render: spp %d, max_depth %d (must be 0..32)", spp, max_depth);
+    CPT_REFUSE_PENDING(c, "cpt_render");
     Frame& f = c->frame;
     if (!c->scene_set) return fail(c, CPT_ERR_STATE, "cpt_render: cpt_set_scene first");
     if (!f.set || !f.rng_set) return fail(c, CPT_ERR_STATE, "cpt_render: cpt_set_frame + cpt_init_rng first");

@@ -2,7 +2,9 @@
 // sampling): rounds of `batch` passes over the 8x8 tiles that are still noisy, the noise map and
 // the round record, and the host-only hook on the criterion.  Each round is the launch cpt_render
 // makes (cpt_capi.cpp's helpers), over a shorter tile order; the kernels around it are
-// cpt_adaptive.hip's.
+// cpt_adaptive.hip's.  The render is cpt_adaptive_begin (checks, buffers, the pilot, round 1
+// queued) and cpt_adaptive_step (one round's read-back, the next round queued), so that one thread
+// can keep a round queued on each of several contexts; cpt_render_adaptive is the two in a loop.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,44 +15,92 @@
 
 using namespace cpt::ctx;
 
-extern "C" {
+namespace {
 
-int cpt_render_adaptive(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, int batch, float rel_error,
-                        int max_depth, uint32_t flags) {
+// One round on the context's stream: cpt_render's launch of `batch` passes over the listed tiles,
+// the moments and keep flags, the compaction into the other order buffer, and the read-back of
+// {tiles kept, pixels rendered, device error word} into the context's pinned words with an event
+// behind it.  No host wait.
+int enqueue_round(cpt_ctx* c) {
+    Frame& f = c->frame;
+    Frame::AdaptivePending& a = f.ad_pending;
+    hipStream_t s = c->stream();
+    ++a.round;
+    // round 1 is cpt_render's own launch (every tile, the caller's accumulate flag); later
+    // rounds add to what the earlier ones left, over the tiles still listed
+    if (a.round > 1) {
+        a.p.accumulate = 1;
+        a.p.n_active = a.active;
+    }
+    HIP_TRY(c, cpt::launch_megakernel(a.p, a.stats, a.aux, c->dbg_max_workgroups, s));
+    cpt::AdaptiveRound r{};
+    r.order = a.p.tile_order;
+    r.n_active = a.active;
+    r.width = c->width;
+    r.n_rows = c->n_rows;
+    r.accum = f.d_accum;
+    r.snap = f.d_ad_snap;
+    r.stat = f.d_ad_stat;
+    r.keep = f.d_ad_keep;
+    r.rel_error = a.rel_error;
+    r.eligible = (long long)a.round * a.batch >= a.min_spp;
+    r.last = a.round >= a.max_rounds;
+    HIP_TRY(c, cpt::launch_tile_noise(r, s));
+    HIP_TRY(c, cpt::launch_compact_order(a.p.tile_order, f.d_ad_keep, a.active, c->width, c->n_rows, f.d_ad_order[a.into],
+                                         f.d_ad_count, s));
+    uint32_t* h = c->h_ad_words.raw();
+    HIP_TRY(c, hipMemcpyAsync(h, f.d_ad_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(h + 2, c->d_work + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipEventRecord(c->ev_round, s));
+    a.queued = true;
+    return CPT_OK;
+}
+
+// cpt_adaptive_begin under the name of the call that makes it (the messages of cpt_render_adaptive
+// are its own).
+int adaptive_begin(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, int batch, float rel_error, int max_depth,
+                   uint32_t flags, const char* who) {
     if (!c || !cam) return CPT_ERR_INVALID_ARG;
     if (max_depth < 0 || max_depth > (int)cpt::MAX_RECURSION_DEPTH_SET)
-        return fail(c, CPT_ERR_INVALID_ARG, "cpt_render_adaptive: max_depth %d (must be 0..32)", max_depth);
+        return fail(c, CPT_ERR_INVALID_ARG, "%s: max_depth %d (must be 0..32)", who, max_depth);
     if (batch < 1 || min_spp < batch || max_spp < min_spp || min_spp % batch || max_spp % batch ||
         (min_spp < 2 * batch && min_spp != max_spp))
         return fail(c, CPT_ERR_INVALID_ARG,
-                    "cpt_render_adaptive: min_spp %d, max_spp %d, batch %d (multiples of batch >= 1, batch <= min_spp <= "
+                    "%s: min_spp %d, max_spp %d, batch %d (multiples of batch >= 1, batch <= min_spp <= "
                     "max_spp, min_spp >= 2 batch unless min_spp == max_spp)",
-                    min_spp, max_spp, batch);
-    if (!(rel_error >= 0.f)) return fail(c, CPT_ERR_INVALID_ARG, "cpt_render_adaptive: rel_error %g", (double)rel_error);
-    if (flags & CPT_PATH_WAVEFRONT)
-        return fail(c, CPT_ERR_UNSUPPORTED, "cpt_render_adaptive: the wavefront path has no adaptive render");
+                    who, min_spp, max_spp, batch);
+    if (!(rel_error >= 0.f)) return fail(c, CPT_ERR_INVALID_ARG, "%s: rel_error %g", who, (double)rel_error);
+    if (flags & CPT_PATH_WAVEFRONT) return fail(c, CPT_ERR_UNSUPPORTED, "%s: the wavefront path has no adaptive render", who);
     if (flags & CPT_SCHEDULE_PREVIOUS)
-        return fail(c, CPT_ERR_UNSUPPORTED, "cpt_render_adaptive: CPT_SCHEDULE_PREVIOUS (use CPT_SCHEDULE_COST)");
+        return fail(c, CPT_ERR_UNSUPPORTED, "%s: CPT_SCHEDULE_PREVIOUS (use CPT_SCHEDULE_COST)", who);
     Frame& f = c->frame;
-    if (!c->scene_set) return fail(c, CPT_ERR_STATE, "cpt_render_adaptive: cpt_set_scene first");
-    if (!f.set || !f.rng_set) return fail(c, CPT_ERR_STATE, "cpt_render_adaptive: cpt_set_frame + cpt_init_rng first");
+    if (f.ad_pending.on) return fail(c, CPT_ERR_STATE, "%s: an adaptive render is pending (cpt_adaptive_step until 0)", who);
+    if (!c->scene_set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_scene first", who);
+    if (!f.set || !f.rng_set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_frame + cpt_init_rng first", who);
     if (cam->width != c->width || cam->height != c->height)
-        return fail(c, CPT_ERR_INVALID_ARG, "cpt_render_adaptive: camera %dx%d vs frame %dx%d", cam->width, cam->height,
-                    c->width, c->height);
+        return fail(c, CPT_ERR_INVALID_ARG, "%s: camera %dx%d vs frame %dx%d", who, cam->width, cam->height, c->width,
+                    c->height);
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream();
     const size_t npix = c->npix(), tiles = n_tiles(c);
-    const int max_rounds = max_spp / batch;
     f.ad_done = false;
     f.ad_active.clear();
     f.ad_passes = 0;
-    if (tiles == 0) {   // a context without rows: nothing to render, an empty record
-        f.ad_done = true;
+    Frame::AdaptivePending a{};
+    a.batch = batch;
+    a.min_spp = min_spp;
+    a.max_rounds = max_spp / batch;
+    a.rel_error = rel_error;
+    a.active = (uint32_t)tiles;
+    if (tiles == 0) {   // a context without rows: nothing to queue; the first step ends it
+        a.on = true;
+        f.ad_pending = a;
         return CPT_OK;
     }
     int rc;
-    const bool aux = (flags & CPT_RENDER_AUX) != 0, stats = (flags & CPT_RENDER_STATS) != 0;
-    if (aux) {
+    a.aux = (flags & CPT_RENDER_AUX) != 0;
+    a.stats = (flags & CPT_RENDER_STATS) != 0;
+    if (a.aux) {
         if ((rc = f.d_normal.ensure(c, npix * 3)) != CPT_OK) return rc;
         if ((rc = f.d_depth.ensure(c, npix)) != CPT_OK) return rc;
     }
@@ -65,58 +115,99 @@ int cpt_render_adaptive(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_
     else
         HIP_TRY(c, hipMemsetAsync(f.d_ad_snap, 0, npix * sizeof(float4), s));
 
-    cpt::KParams p;
-    fill_params(c, cam, batch, max_depth, flags, p);
+    fill_params(c, cam, batch, max_depth, flags, a.p);
+    c->have_timing = false;   // ev_start .. ev_stop span the rounds: no timing until the last step
     HIP_TRY(c, hipEventRecord(c->ev_start, s));
     if (flags & CPT_SCHEDULE_COST) {
         // one pilot, sized for the whole render; the rounds filter its order
-        if ((rc = cost_pilot(c, p, cost_pilot_passes(max_spp), s)) != CPT_OK) return rc;
-        p.tile_order = f.d_tile_order;
+        if ((rc = cost_pilot(c, a.p, cost_pilot_passes(max_spp), s)) != CPT_OK) return rc;
+        a.p.tile_order = f.d_tile_order;
     }
-    if ((rc = consolidation_slab(c, p, batch, flags)) != CPT_OK) return rc;
+    if ((rc = consolidation_slab(c, a.p, batch, flags)) != CPT_OK) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_main, s));
-    uint32_t active = (uint32_t)tiles;
-    int into = 0;   // the order buffer the next compaction writes
-    for (int round = 1; active > 0; ++round) {
-        // round 1 is cpt_render's own launch (every tile, the caller's accumulate flag); later
-        // rounds add to what the earlier ones left, over the tiles still listed
-        if (round > 1) {
-            p.accumulate = 1;
-            p.n_active = active;
-        }
-        HIP_TRY(c, cpt::launch_megakernel(p, stats, aux, c->dbg_max_workgroups, s));
-        cpt::AdaptiveRound a{};
-        a.order = p.tile_order;
-        a.n_active = active;
-        a.width = c->width;
-        a.n_rows = c->n_rows;
-        a.accum = f.d_accum;
-        a.snap = f.d_ad_snap;
-        a.stat = f.d_ad_stat;
-        a.keep = f.d_ad_keep;
-        a.rel_error = rel_error;
-        a.eligible = (long long)round * batch >= min_spp;
-        a.last = round >= max_rounds;
-        HIP_TRY(c, cpt::launch_tile_noise(a, s));
-        HIP_TRY(c, cpt::launch_compact_order(p.tile_order, f.d_ad_keep, active, c->width, c->n_rows, f.d_ad_order[into],
-                                             f.d_ad_count, s));
-        uint32_t got[2] = {0, 0};
-        HIP_TRY(c, hipMemcpyAsync(got, f.d_ad_count, sizeof(got), hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipStreamSynchronize(s));
-        if ((rc = check_device_error(c)) != CPT_OK) return rc;
-        if (got[0] > active) return fail(c, CPT_ERR_DEVICE, "cpt_render_adaptive: %u of %u tiles kept", got[0], active);
-        f.ad_active.push_back(active);
-        f.ad_passes += (uint64_t)got[1] * (uint64_t)batch;
-        active = got[0];
-        p.tile_order = f.d_ad_order[into];
-        into ^= 1;
+    f.ad_pending = a;
+    if ((rc = enqueue_round(c)) != CPT_OK) {
+        f.ad_pending = Frame::AdaptivePending{};
+        return rc;
     }
-    HIP_TRY(c, hipEventRecord(c->ev_stop, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    c->last_launches = (int)f.ad_active.size();
-    c->have_timing = true;
-    f.prev_d_valid = false;   // CPT_SCHEDULE_PREVIOUS counts draws from the next render on
+    f.ad_pending.on = true;
+    return CPT_OK;
+}
+
+// The pending round's result, then the next round or the end of the render.
+int adaptive_step(cpt_ctx* c, int* active_tiles, const char* who) {
+    Frame& f = c->frame;
+    Frame::AdaptivePending& a = f.ad_pending;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream();
+    if (a.queued) {
+        // the read-back only: what the stream holds behind it (nothing, today) is not waited for
+        HIP_TRY(c, hipEventSynchronize(c->ev_round));
+        a.queued = false;
+        const volatile uint32_t* h = c->h_ad_words.get();
+        const uint32_t kept = h[0], pixels = h[1], dev_err = h[2];
+        if (dev_err) {
+            const int rc = check_device_error(c);   // reports and clears the word
+            return rc != CPT_OK ? rc : fail(c, CPT_ERR_DEVICE, "%s: device error 0x%x", who, dev_err);
+        }
+        if (kept > a.active) return fail(c, CPT_ERR_DEVICE, "%s: %u of %u tiles kept", who, kept, a.active);
+        f.ad_active.push_back(a.active);
+        f.ad_passes += (uint64_t)pixels * (uint64_t)a.batch;
+        a.active = kept;
+        a.p.tile_order = f.d_ad_order[a.into];
+        a.into ^= 1;
+    }
+    if (a.active > 0) {
+        if (int rc = enqueue_round(c)) return rc;
+        *active_tiles = (int)a.active;
+        return CPT_OK;
+    }
+    if (a.round > 0) {   // rounds ran (a context without rows has none, and no timing)
+        HIP_TRY(c, hipEventRecord(c->ev_stop, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        c->last_launches = (int)f.ad_active.size();
+        c->have_timing = true;
+        f.prev_d_valid = false;   // CPT_SCHEDULE_PREVIOUS counts draws from the next render on
+    }
+    f.ad_pending = Frame::AdaptivePending{};
     f.ad_done = true;
+    *active_tiles = 0;
+    return CPT_OK;
+}
+
+// A failed step ends the render: nothing pending, no adaptive result; the stream is drained so
+// that what it still holds cannot run into the caller's next call.
+int adaptive_step_checked(cpt_ctx* c, int* active_tiles, const char* who) {
+    if (!c->frame.ad_pending.on) return fail(c, CPT_ERR_STATE, "%s: no adaptive render is pending (cpt_adaptive_begin first)", who);
+    const int rc = adaptive_step(c, active_tiles, who);
+    if (rc != CPT_OK) {
+        c->frame.ad_pending = Frame::AdaptivePending{};
+        c->frame.ad_done = false;
+        (void)hipStreamSynchronize(c->stream());
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cpt_adaptive_begin(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, int batch, float rel_error,
+                       int max_depth, uint32_t flags) {
+    return adaptive_begin(c, cam, min_spp, max_spp, batch, rel_error, max_depth, flags, "cpt_adaptive_begin");
+}
+
+int cpt_adaptive_step(cpt_ctx* c, int* active_tiles) {
+    if (!c || !active_tiles) return CPT_ERR_INVALID_ARG;
+    return adaptive_step_checked(c, active_tiles, "cpt_adaptive_step");
+}
+
+int cpt_render_adaptive(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, int batch, float rel_error,
+                        int max_depth, uint32_t flags) {
+    static const char who[] = "cpt_render_adaptive";
+    if (int rc = adaptive_begin(c, cam, min_spp, max_spp, batch, rel_error, max_depth, flags, who)) return rc;
+    for (int active = 1; active > 0;)
+        if (int rc = adaptive_step_checked(c, &active, who)) return rc;
     return CPT_OK;
 }
 

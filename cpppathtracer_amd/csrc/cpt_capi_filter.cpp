@@ -28,6 +28,7 @@ int cpt_filter_frame(cpt_ctx* c, int levels, float sigma_l, int normal_sharpness
         return fail(c, CPT_ERR_INVALID_ARG,
                     "cpt_filter_frame: levels %d (0..8), sigma_l %g (finite, >= 0), normal_sharpness_log2 %d (0..10)", levels,
                     (double)sigma_l, normal_sharpness_log2);
+    CPT_REFUSE_PENDING(c, "cpt_filter_frame");
     Frame& f = c->frame;
     if (!f.set || c->n_rows != c->height) return fail(c, CPT_ERR_STATE, "cpt_filter_frame: needs a full frame");
     for (int y = 0; y < c->height; ++y)

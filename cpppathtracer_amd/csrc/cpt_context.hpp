@@ -66,6 +66,18 @@ struct Frame {
     bool ad_done = false;                  // an adaptive render has completed on this frame
     std::vector<uint32_t> ad_active;       // its rounds: the tiles each one rendered
     uint64_t ad_passes = 0;                // its pixel passes, all rounds
+    // an adaptive render between cpt_adaptive_begin and the cpt_adaptive_step that returns 0: what
+    // the next round is launched with; `queued`: a round and its read-back are on the stream
+    struct AdaptivePending {
+        bool on = false, queued = false;
+        cpt::KParams p{};
+        bool stats = false, aux = false;
+        int batch = 0, min_spp = 0, max_rounds = 0;
+        float rel_error = 0.f;
+        int round = 0;          // rounds queued so far
+        uint32_t active = 0;    // tiles of the round queued (or to queue) next
+        int into = 0;           // the order buffer the next compaction writes
+    } ad_pending;
     // a-trous filter (cpt_capi_filter.cpp; allocated on the frame's first cpt_filter_frame): the two
     // planes the levels ping-pong between (rgb + variance of the mean), each pixel's validity, and
     // the plane that holds the last call's result (-1: no call yet)
@@ -156,6 +168,11 @@ struct cpt_ctx {
     };
     std::vector<GatherMap> gather_maps;
     DevBuf<float4> d_gather;
+    DevBuf<float> d_gather_stat;   // a staged source's moment planes (planar [4][src npix])
+    // adaptive rounds (cpt_adaptive_begin / _step): the read-back of a round, {tiles kept, pixels
+    // rendered, device error word}, and the event recorded behind it
+    cpt::ctx::HostPinned<uint32_t> h_ad_words;
+    DevEvent ev_round;
     DevEvent ev_ready;    // a gather's source: its queued work
     DevEvent ev_gathered; // a gather's destination: the stitch done
     DevEvent ev_caller;   // a device copy's caller stream: its queued work
@@ -173,6 +190,14 @@ struct cpt_ctx {
 
 namespace cpt {
 namespace ctx {
+
+// CPT_ERR_STATE from `who` while an adaptive render is pending on the context (between
+// cpt_adaptive_begin and the cpt_adaptive_step that returns 0): its rounds own the frame's buffers.
+#define CPT_REFUSE_PENDING(ctx, who)                                                                              \
+    do {                                                                                                          \
+        if ((ctx)->frame.ad_pending.on)                                                                           \
+            return fail((ctx), CPT_ERR_STATE, who ": an adaptive render is pending (cpt_adaptive_step until 0)"); \
+    } while (0)
 
 // Drain the context's stream, then report a device-side error of the work it ran.
 int check_device_error(cpt_ctx* c);

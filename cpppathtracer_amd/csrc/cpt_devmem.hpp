@@ -1,5 +1,6 @@
 // cpt_devmem.hpp — the C-ABI's error helpers (fail, HIP_TRY) and the move-only owners of what a
-// context holds on the device: DevBuf<T> (a unique_ptr with a capacity), DevEvent, DevStream.
+// context holds on the device: DevBuf<T> (a unique_ptr with a capacity), HostPinned<T> (pinned host
+// words a stream writes), DevEvent, DevStream.
 // A default-constructed owner is empty; assigning a fresh one releases what it held.  Host code only.
 #pragma once
 
@@ -69,6 +70,31 @@ public:
 private:
     T* p_ = nullptr;
     size_t cap_ = 0;
+};
+
+// A few page-locked host words a stream copies results into: the copy is then truly asynchronous
+// (a read-back into pageable memory makes hipMemcpyAsync wait), and the host reads the words after
+// waiting for an event recorded behind it.
+template <typename T>
+class HostPinned {
+public:
+    HostPinned() = default;
+    HostPinned(const HostPinned&) = delete;
+    HostPinned& operator=(const HostPinned&) = delete;
+    ~HostPinned() { if (p_) (void)hipHostFree(p_); }
+    // `count` (> 0) elements, once; an owner that already holds memory keeps it.
+    hipError_t alloc(size_t count) {
+        if (p_) return hipSuccess;
+        const hipError_t e = hipHostMalloc((void**)&p_, count * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) p_ = nullptr;
+        return e;
+    }
+    // volatile: the device writes the words behind the compiler's back
+    volatile T* get() const { return p_; }
+    T* raw() const { return p_; }
+
+private:
+    T* p_ = nullptr;
 };
 
 class DevEvent {

@@ -6,6 +6,7 @@
 //                         it checks so the 8 KB table exists once
 //   k_denoise_rows        Denoising + Mix (path_tracer.cu:177-254);  launch_denoise_mix
 //   k_stitch_rows         the row-tile gather (cpt_gather_rows);  launch_stitch_rows
+//   k_stitch_moments      the gather of a source's adaptive moments;  launch_stitch_moments
 //
 // Reference semantics per function are cited inline; DESIGN.md has the data layout and the
 // roofline of each kernel.
@@ -506,6 +507,32 @@ hipError_t launch_stitch_rows(const float4* src_acc, const float* src_nrm, const
     if (width <= 0 || n_rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_stitch_rows, dim3((width + 255) / 256, n_rows), dim3(256), 0, stream, src_acc, src_nrm, src_dep,
                        dst_row, width, acc, nrm, dep);
+    return hipGetLastError();
+}
+
+// The adaptive moments of a source's rows (planar [4][src_npix]: m1, m2, k, rel) to the same
+// destination rows of the destination's planes (planar [4][dst_npix]).  One lane per pixel, its
+// four planes' words: each wave reads and writes 256 contiguous bytes per plane, and a lane's four
+// loads are independent.
+__global__ void __launch_bounds__(256) k_stitch_moments(const float* __restrict__ src, size_t src_npix,
+                                                        const int32_t* __restrict__ dst_row, int width,
+                                                        float* __restrict__ dst, size_t dst_npix) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r = blockIdx.y;
+    if (x >= width) return;
+    const size_t s = (size_t)r * width + x, d = (size_t)dst_row[r] * width + x;
+    const float m1 = src[s], m2 = src[src_npix + s], k = src[2 * src_npix + s], rel = src[3 * src_npix + s];
+    dst[d] = m1;
+    dst[dst_npix + d] = m2;
+    dst[2 * dst_npix + d] = k;
+    dst[3 * dst_npix + d] = rel;
+}
+
+hipError_t launch_stitch_moments(const float* src, size_t src_npix, const int32_t* dst_row, int width, int n_rows,
+                                 float* dst, size_t dst_npix, hipStream_t stream) {
+    if (width <= 0 || n_rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_stitch_moments, dim3((width + 255) / 256, n_rows), dim3(256), 0, stream, src, src_npix, dst_row,
+                       width, dst, dst_npix);
     return hipGetLastError();
 }
 }  // namespace cpt

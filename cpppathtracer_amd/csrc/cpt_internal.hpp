@@ -183,6 +183,10 @@ hipError_t launch_selftest_qdiv(int which, uint64_t n, uint64_t seed, unsigned l
 hipError_t launch_selftest_dn_weight(int which, uint64_t n, unsigned long long* out, int out_len, hipStream_t stream);
 hipError_t launch_stitch_rows(const float4* src_acc, const float* src_nrm, const float* src_dep, const int32_t* dst_row,
                               int width, int n_rows, float4* acc, float* nrm, float* dep, hipStream_t stream);
+// The gather's moments (cpt_display.hip): the four planes of `src` (planar [4][src_npix], n_rows
+// rows of `width`) to rows dst_row[r] of `dst` (planar [4][dst_npix]).
+hipError_t launch_stitch_moments(const float* src, size_t src_npix, const int32_t* dst_row, int width, int n_rows,
+                                 float* dst, size_t dst_npix, hipStream_t stream);
 // out_host (nullable): the device alias of a pinned host frame, written beside `out`; accum /
 // normal / depth hold the context's ctx_rows rows from row0; sink: a
 // device buffer of DN_SINK_SLOTS float4s the strip kernel's lanes without an output pixel store to

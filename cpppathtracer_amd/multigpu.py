@@ -14,6 +14,43 @@ import torch.distributed as dist
 from . import tiling
 
 
+def render_adaptive_tiled(frame, tiles, cam, min_spp, max_spp, batch, rel_error, max_depth, flags=0):
+    """An adaptive render over row tiles in one process: `tiles` are Renderers whose frames hold
+    the rows of a partition (each on its own device, or several on one), `frame` the Renderer of
+    the full frame they are gathered into.  Every tile's first round is queued (adaptive_begin),
+    then the unfinished tiles are stepped in turn from this thread, so every device has a round
+    queued while the host waits on another; then every tile is gathered, moments included, and the
+    frame and the tiles are synchronised.  With tiles of whole 8-row blocks in ascending order
+    (tiling.partition_rows, rows_of_owner) the frame, its moments and noise map, and what
+    filter_frame makes of them equal one Renderer's render_adaptive of the frame bit for bit.
+    Returns each tile's (rounds, passes)."""
+    pending = []
+    try:
+        for t in tiles:
+            t.adaptive_begin(cam, min_spp, max_spp, batch, rel_error, max_depth, flags)
+            pending.append(t)
+        while pending:
+            pending = [t for t in pending if t.adaptive_step() > 0]
+    except Exception:
+        # leave no tile pending: the others' rounds run to their end (a failed step ended its own)
+        for t in pending:
+            try:
+                while t.adaptive_step() > 0:
+                    pass
+            except Exception:
+                pass
+        raise
+    for t in tiles:
+        frame.gather_rows(t)
+    frame.synchronize()
+    out = []
+    for t in tiles:
+        t.synchronize()
+        info = t.adaptive_info()
+        out.append((info["rounds"], info["passes_done"]))
+    return out
+
+
 class TileGather:
     """Buffers and the collective for one rank's share of a row-tiled frame."""
 

@@ -184,11 +184,33 @@ class Renderer:
         c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
         self._check(self._L.cpt_render_adaptive(self._ctx, _p(c), int(min_spp), int(max_spp), int(batch),
                                                 ctypes.c_float(rel_error), int(max_depth), int(flags)))
+        return self.adaptive_info()
+
+    def adaptive_info(self):
+        """cpt_adaptive_info of the last adaptive render: {"rounds", "active_tiles" (uint32 per
+        round), "passes_done" (pixel passes)}."""
         rounds, passes = ctypes.c_int(0), ctypes.c_uint64(0)
-        active = np.zeros(max(1, int(max_spp) // int(batch)), dtype=np.uint32)
+        self._check(self._L.cpt_adaptive_info(self._ctx, ctypes.byref(rounds), None, 0, ctypes.byref(passes)))
+        active = np.zeros(max(1, rounds.value), dtype=np.uint32)
         self._check(self._L.cpt_adaptive_info(self._ctx, ctypes.byref(rounds), _p(active), active.size,
                                               ctypes.byref(passes)))
         return {"rounds": rounds.value, "active_tiles": active[:rounds.value].copy(), "passes_done": int(passes.value)}
+
+    def adaptive_begin(self, cam, min_spp, max_spp, batch, rel_error, max_depth, flags=0):
+        """cpt_adaptive_begin: render_adaptive's checks and its first round, queued without a host
+        wait.  Until adaptive_step returns 0 the render is pending: render, render_adaptive,
+        adaptive_begin, set_frame, filter_frame and gather_rows with this Renderer raise
+        CPT_ERR_STATE."""
+        c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
+        self._check(self._L.cpt_adaptive_begin(self._ctx, _p(c), int(min_spp), int(max_spp), int(batch),
+                                               ctypes.c_float(rel_error), int(max_depth), int(flags)))
+
+    def adaptive_step(self) -> int:
+        """cpt_adaptive_step: waits for the queued round, then queues the next one and returns the
+        tiles it renders, or ends the render and returns 0 (adaptive_info then has its record)."""
+        active = ctypes.c_int(0)
+        self._check(self._L.cpt_adaptive_step(self._ctx, ctypes.byref(active)))
+        return active.value
 
     def read_noise(self):
         """The last render_adaptive's noise map (cpt_read_noise): each pixel's relative standard

@@ -8,7 +8,8 @@
 //
 // --devices N row-tiles the image over N contexts (PathTracer::SetDevices: device i % visible
 // devices, so N > the GPU count puts several tiles on one GPU) and gathers each pass's tiles
-// into one frame; the image is the single-device image, bit for bit.
+// into one frame; the image is the single-device image, bit for bit.  So are --adaptive and
+// --filter with it: the tiles' rounds run side by side and their moments are gathered too.
 //
 // --dump-scene writes the objects as SceneBVH::BuildBVH copied them (cpt_object records, the
 // C-ABI layout) and exits without rendering (no GPU needed).

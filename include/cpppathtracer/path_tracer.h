@@ -68,8 +68,11 @@ public:
     // Synchronous adaptive render into a restarted accumulator (cpt_render_adaptive): rounds of
     // `batch` passes over the 8x8 tiles whose pixels have not all reached a relative standard
     // error of rel_error; none stops before min_spp, all at max_spp.  Each pixel ends as a
-    // Render of its own pass count would leave it.  Single device only.  rounds / passes_done
-    // (optional): the rounds run and the pixel passes of all of them.
+    // Render of its own pass count would leave it.  With SetDevices every tile's rounds are queued
+    // on its own device and stepped in turn from this thread (cpt_adaptive_begin / _step), then
+    // the tiles and their moments are gathered: the frame, the noise map and the filter's result
+    // are those of one device, bit for bit.  rounds / passes_done (optional): the rounds run (the
+    // most of any tile) and the pixel passes of all of them (summed over the tiles).
     bool RenderAdaptive(int min_spp, int max_spp, int batch, float rel_error, int* rounds = nullptr,
                         uint64_t* passes_done = nullptr);
     // The last RenderAdaptive's per-pixel relative standard error, float[width*height].
@@ -117,6 +120,8 @@ private:
     bool BindTextures(Tile& t, const std::vector<cpt_object>& objs);
     bool EnsureFrame(const MotionalCamera& cam);
     bool RenderPass(MotionalCamera& cam, int spp, bool accumulate);
+    bool RenderAdaptiveTiles(MotionalCamera& cam, int min_spp, int max_spp, int batch, float rel_error, uint32_t flags,
+                             int* rounds, uint64_t* passes_done);
     void PipelineLoop();
     bool Fail(const char* what, cpt_ctx* ctx = nullptr);
     cpt_ctx* FrameCtx() const { return frame_ ? frame_ : (tiles_.empty() ? nullptr : tiles_[0].ctx); }

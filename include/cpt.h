@@ -292,9 +292,26 @@ int cpt_tile_costs(cpt_ctx* ctx, const cpt_camera* cam, int passes, int max_dept
  * Rules (else CPT_ERR_INVALID_ARG): batch >= 1; min_spp and max_spp multiples of batch;
  * batch <= min_spp <= max_spp; min_spp >= 2 * batch unless min_spp == max_spp; rel_error >= 0.
  * CPT_ERR_UNSUPPORTED: CPT_PATH_WAVEFRONT, CPT_SCHEDULE_PREVIOUS.  Synchronous: the list's length
- * is read back after every round. */
+ * is read back after every round (cpt_adaptive_begin, then cpt_adaptive_step until it gives 0). */
 int cpt_render_adaptive(cpt_ctx* ctx, const cpt_camera* cam, int min_spp, int max_spp, int batch, float rel_error,
                         int max_depth, uint32_t flags);
+/* The adaptive render in two calls, for a caller that drives several contexts from one thread (row
+ * tiles on several devices): cpt_adaptive_begin checks what cpt_render_adaptive checks, queues round
+ * 1 with the read-back of its result on the context's stream and returns without waiting.
+ * cpt_adaptive_step waits for the queued round's read-back alone (an event behind it), records the
+ * round, and either queues the next round and returns the tiles it renders in *active_tiles, or,
+ * when no tile is left, ends the render and returns 0 there; a context without rows ends at its
+ * first step.  Call begin on every context, then step the unfinished ones in turn: every device
+ * then has a round queued while the host waits on another.  The result is cpt_render_adaptive's.
+ * Pending state: between a successful begin and the step that returns 0 the rounds own the
+ * frame's buffers, and cpt_render, cpt_render_adaptive, cpt_adaptive_begin, cpt_set_frame,
+ * cpt_filter_frame and cpt_gather_rows (the context as source or destination) return
+ * CPT_ERR_STATE; so does cpt_adaptive_step with nothing pending, and the read-outs of an adaptive
+ * result (there is none yet).  A step that fails ends the render: nothing is pending and the frame
+ * holds no adaptive result.  cpt_destroy waits for a pending context's stream and frees it. */
+int cpt_adaptive_begin(cpt_ctx* ctx, const cpt_camera* cam, int min_spp, int max_spp, int batch, float rel_error,
+                       int max_depth, uint32_t flags);
+int cpt_adaptive_step(cpt_ctx* ctx, int* active_tiles);
 /* The last adaptive render since cpt_set_frame (CPT_ERR_STATE if none).  cpt_read_noise: each
  * pixel's relative standard error as its last round left it (the criterion's left side over its
  * right side's max(mean, 1e-3); +inf with fewer than two batch means), [n_rows*width], capacity in
@@ -330,8 +347,8 @@ int cpt_write_moments(cpt_ctx* ctx, const float* planar4, size_t count);
  * sharpness 7 (the measurements behind sigma_l).  Bad arguments: CPT_ERR_INVALID_ARG.
  * Needs (else CPT_ERR_STATE) a full frame (rows == NULL, as cpt_denoise_mix), moments
  * (cpt_render_adaptive or cpt_write_moments) and first-hit normals (CPT_RENDER_AUX or
- * cpt_write_aux).  A row-tiled render filters on each tile's own context: cpt_gather_rows does not
- * carry moments.  Reads the accumulator, the moments and the normals and writes none of them (nor
+ * cpt_write_aux).  A row-tiled adaptive render is filtered on the frame context its tiles were
+ * gathered into: cpt_gather_rows carries the moments.  Reads the accumulator, the moments and the normals and writes none of them (nor
  * the RNG); the result lives in buffers of its own until the next call or cpt_set_frame.
  * Asynchronous, on the context's stream. */
 int cpt_filter_frame(cpt_ctx* ctx, int levels, float sigma_l, int normal_sharpness_log2);
@@ -368,7 +385,15 @@ int cpt_copy_accum_device(cpt_ctx* ctx, void* device_dst, size_t bytes, void* ca
  * same one.  Asynchronous: ordered after src's queued work and before src's later work by
  * events, with no host wait, so several gathers queue back to back; dst then holds the stitched
  * frame for its next call (cpt_synchronize, cpt_read_accum, cpt_read_aux, cpt_denoise_mix).
- * src's device errors are reported by src's own next synchronising call. */
+ * src's device errors are reported by src's own next synchronising call.
+ * When src holds an adaptive result (cpt_render_adaptive, the begin / step pair, or
+ * cpt_write_moments) its four moment planes are placed too, by a second kernel behind the first.
+ * A dst without an adaptive result of its own first gets m1 = m2 = k = 0 and +inf noise everywhere
+ * (a pixel before its second batch: rows no source covers are invalid for the filter), and dst
+ * then holds an adaptive result with an empty round record, as after cpt_write_moments:
+ * cpt_read_noise, cpt_read_moments and cpt_filter_frame work on it.  When the tiles are whole 8-row
+ * blocks in ascending order the stitched moments are those of one context's adaptive render of the
+ * frame.  A src without an adaptive result leaves dst's moments alone. */
 int cpt_gather_rows(cpt_ctx* dst, cpt_ctx* src);
 /* How the last cpt_gather_rows(dst, src) reached src's buffers (-1: no gather of the pair yet):
  * the stitch read them in place on the same device, read them over xGMI with peer access
