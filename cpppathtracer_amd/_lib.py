@@ -55,6 +55,7 @@ PROTOTYPES = {
     "cpt_get_raw_counters": (_I, [_P, _P]),
     "cpt_get_walk_info": (_I, [_P, _P]),
     "cpt_debug_read_nodes": (_I, [_P, _P, _SZ, _P]),
+    "cpt_debug_read_tile_order": (_I, [_P, _I, _P, _SZ, _P]),
     "cpt_measure_read_bandwidth": (_I, [_P, _SZ, _I, _P]),
     "cpt_measure_read_pattern": (_I, [_P, _I, _SZ, _I, _P]),
     "cpt_cap_disk_bound": (_I, [ctypes.c_float, _P]),

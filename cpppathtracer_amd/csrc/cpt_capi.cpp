@@ -268,6 +268,10 @@ int cpt_init_rng(cpt_ctx* c, uint64_t seed) {
     if ((rc = f.d_scratch_w.ensure(c, 5 * (size_t)c->width)) != CPT_OK) return rc;
     if ((rc = f.d_scratch_m.ensure(c, (size_t)c->n_rows * 800)) != CPT_OK) return rc;
     f.prev_d_valid = false;   // CPT_SCHEDULE_PREVIOUS counts draws from the next render on
+    // and its order came from the streams this call replaces: the next such render runs in
+    // raster order and rebuilds it (the order stayed valid across a re-seed before)
+    f.prev_order_valid = false;
+    f.prev_since_order = 0;
     uint32_t st[6];
     curand_seed_state(seed, st);
     HIP_TRY(c, cpt::launch_init_rng(c->d_jumps, st, c->width, f.d_rows, c->n_rows, f.d_scratch_w, f.d_scratch_m,

@@ -52,6 +52,34 @@ int cpt_debug_read_nodes(cpt_ctx* c, void* out, size_t capacity_bytes, size_t* n
     return CPT_OK;
 }
 
+int cpt_debug_read_tile_order(cpt_ctx* c, int which, uint32_t* out, size_t capacity, size_t* n) {
+    if (!c || !out || !n) return CPT_ERR_INVALID_ARG;
+    if (which < 0 || which > 2) return fail(c, CPT_ERR_INVALID_ARG, "cpt_debug_read_tile_order: which %d (0..2)", which);
+    const Frame& f = c->frame;
+    const uint32_t* src = nullptr;   // stays null for the pending round's list without an order: 0, 1, 2, ...
+    size_t len = n_tiles(c);
+    if (which == 0) {
+        if (!f.set || !f.d_tile_order) return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no cost pilot on this frame");
+        src = f.d_tile_order;
+    } else if (which == 1) {
+        if (!f.set || !f.prev_order_valid)
+            return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no CPT_SCHEDULE_PREVIOUS order on this frame");
+        src = f.d_prev_order;
+    } else {
+        if (!f.ad_pending.on) return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no adaptive render is pending");
+        src = f.ad_pending.p.tile_order;
+        len = f.ad_pending.active;
+    }
+    *n = len;
+    if (capacity < len) return fail(c, CPT_ERR_INVALID_ARG, "cpt_debug_read_tile_order: %zu < %zu tiles", capacity, len);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (src && len) HIP_TRY(c, hipMemcpyAsync(out, src, len * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream()));
+    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    if (!src)
+        for (size_t i = 0; i < len; ++i) out[i] = (uint32_t)i;
+    return CPT_OK;
+}
+
 int cpt_math_batch(cpt_ctx* c, int op,const float* a, const float* b, float* out, size_t n) {
     if (!c || !a || !b || !out) return CPT_ERR_INVALID_ARG;
     if (n == 0) return CPT_OK;

@@ -394,6 +394,16 @@ class Renderer:
             self._check(self._L.cpt_debug_read_nodes(self._ctx, _p(out), out.size, ctypes.byref(n)))
         return out
 
+    def debug_tile_order(self, which):
+        """DIAGNOSTIC: a device-built tile list (cpt_debug_read_tile_order) as uint32 tile ids:
+        which = 0 the cost schedule's order, 1 the CPT_SCHEDULE_PREVIOUS order, 2 the list the
+        pending adaptive round renders.  Waits for the context's stream."""
+        ty, tx = (self.n_rows + 7) // 8, (self.width + 7) // 8
+        out = np.zeros(max(1, ty * tx), dtype=np.uint32)
+        n = ctypes.c_size_t(0)
+        self._check(self._L.cpt_debug_read_tile_order(self._ctx, int(which), _p(out), ty * tx, ctypes.byref(n)))
+        return out[:n.value].copy()
+
     def measure_read_pattern(self, bytes_per_lane, nbytes=1 << 30, iters=1):
         """DIAGNOSTIC: GB/s of a streaming read in one of the display kernel's access shapes
         (cpt_measure_read_pattern: 4, 12 or 16 bytes per lane)."""

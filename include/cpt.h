@@ -441,6 +441,20 @@ int cpt_get_walk_info(cpt_ctx* ctx, int32_t* out4);
  * no kernel and changes no state.  No reference counterpart: a test hook for the device refit
  * (an addition to the ABI: CPT_ABI_VERSION stays 1). */
 int cpt_debug_read_nodes(cpt_ctx* ctx, void* out, size_t capacity_bytes, size_t* n_bytes);
+/* DIAGNOSTIC: one of the device-built lists of 8x8 tile ids the megakernel dequeues from, copied to
+ * `out` (capacity in ids); *n receives its length.  which = 0: the cost schedule's order, all the
+ * frame's tiles heaviest first, as the frame's last pilot left it (a CPT_SCHEDULE_COST render,
+ * cpt_tile_costs, cpt_adaptive_begin with the flag).  which = 1: the order the last
+ * CPT_SCHEDULE_PREVIOUS rebuild left for the next such render.  which = 2: the list the pending
+ * adaptive round renders, between a successful cpt_adaptive_begin and the cpt_adaptive_step that
+ * returns 0 (round 1 without the cost schedule has no list on the device: 0, 1, 2, ...).
+ * CPT_ERR_STATE when the frame holds no such list; CPT_ERR_INVALID_ARG for another `which` or a
+ * capacity below the length (nothing written).  WAITS: the copy is queued on the context's stream
+ * and the stream is drained, so with which = 2 the call returns after the queued round (which only
+ * reads that list: its compaction writes the other buffer).  Launches no kernel and changes no
+ * state: the cpt_adaptive_step after it behaves as without it.  No reference counterpart: a test
+ * hook for the tile lists (an addition to the ABI: CPT_ABI_VERSION stays 1). */
+int cpt_debug_read_tile_order(cpt_ctx* ctx, int which, uint32_t* out, size_t capacity, size_t* n);
 /* Device time of the last cpt_render (HIP events on the launch stream); waits for it. */
 int cpt_last_render_ms(cpt_ctx* ctx, float* ms);
 /* Average device time of one launch of the last cpt_render's dominant kernel: the megakernel

@@ -96,10 +96,22 @@ def run(snaps, width, n_rows, batch, min_spp, max_spp, t, acc0=None):
         stop[leave] = r
         active = active & ~leave
     px_stop = stop[tile]
-    accum = np.stack([snaps[px_stop[i] - 1][0][i] for i in range(npix)])
-    rng = np.stack([snaps[px_stop[i] - 1][1][:, i] for i in range(npix)], axis=1)
+    assert (px_stop >= 1).all()   # every tile has left the list by the last round
+
+    def at_stop(planes, axis):   # each pixel (along `axis`) from the snapshot of its stop round
+        out = planes[0].copy()
+        for r in range(2, len(snaps) + 1):
+            sel = np.nonzero(px_stop == r)[0]
+            if axis == 0:
+                out[sel] = planes[r - 1][sel]
+            else:
+                out[:, sel] = planes[r - 1][:, sel]
+        return out
+
+    accum = at_stop([s[0] for s in snaps], 0)
+    rng = at_stop([s[1] for s in snaps], 1)
     normal = None
     if snaps[0][2] is not None:
-        normal = np.stack([snaps[px_stop[i] - 1][2][i] for i in range(npix)])
+        normal = at_stop([s[2] for s in snaps], 0)
     return dict(stop=stop, active=np.array(counts, dtype=np.uint32), accum=accum, rng=rng, normal=normal, noise=rel,
                 passes_done=int(px_stop.sum()) * batch)
