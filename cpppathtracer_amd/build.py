@@ -22,6 +22,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_kernels.hip"),
     os.path.join(CSRC, "cpt_wavefront.hip"),
     os.path.join(CSRC, "cpt_capi.cpp"),
+    os.path.join(CSRC, "cpt_capi_render.cpp"),
     os.path.join(CSRC, "cpt_capi_gather.cpp"),
     os.path.join(CSRC, "cpt_capi_display.cpp"),
     os.path.join(CSRC, "cpt_capi_probes.cpp"),

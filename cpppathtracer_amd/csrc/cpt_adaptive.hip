@@ -11,29 +11,20 @@
 
 #include "cpt_adaptive.hpp"
 #include "cpt_internal.hpp"
+#include "cpt_tiles.hpp"
 
 namespace cpt {
 
-namespace {
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {   // set lanes of `mask` below this one
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-__device__ __forceinline__ uint32_t count64(uint64_t m) {
-    return (uint32_t)__builtin_popcount((uint32_t)m) + (uint32_t)__builtin_popcount((uint32_t)(m >> 32));
-}
-}  // namespace
-
-// One wave64 per position of the active list; lane k = pixel k of the tile (decode_pixel's
-// layout, cpt_megakernel.hip).  Lanes outside the frame (partial tiles) do nothing and count as
+// One wave64 per position of the active list; lane k = pixel k of the tile
+// (TileGrid::pixel).  Lanes outside the frame (partial tiles) do nothing and count as
 // converged.  The tile's flag is a ballot: no LDS.
 __global__ void __launch_bounds__(64) k_tile_noise(const AdaptiveRound a) {
     const uint32_t i = blockIdx.x;   // < a.n_active: the grid's size
     const uint32_t tile = a.order ? a.order[i] : i;
-    const int tiles_x = (a.width + 7) >> 3;
     const int k = threadIdx.x;
-    const int x = (int)(tile % tiles_x) * 8 + (k & 7), ri = (int)(tile / tiles_x) * 8 + (k >> 3);
+    int x, ri;
     bool open = false;
-    if (x < a.width && ri < a.n_rows) {
+    if (TileGrid{a.width, a.n_rows}.pixel(tile, k, x, ri)) {
         const size_t npix = (size_t)a.n_rows * a.width;
         const size_t pix = (size_t)ri * a.width + x;
         const float4 S = a.accum[pix], P = a.snap[pix];
@@ -64,7 +55,7 @@ __global__ void __launch_bounds__(COMPACT_BLOCK) k_compact_order(const uint32_t*
     constexpr int WAVES = COMPACT_BLOCK / 64;
     __shared__ uint32_t s_cnt[WAVES], s_px[WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int tiles_x = (width + 7) >> 3;
+    const TileGrid grid{width, n_rows};
     uint32_t base = 0;   // uniform: tiles kept before this chunk
     uint32_t px = 0;
     for (uint32_t i0 = 0; i0 < n; i0 += COMPACT_BLOCK) {
@@ -74,11 +65,10 @@ __global__ void __launch_bounds__(COMPACT_BLOCK) k_compact_order(const uint32_t*
         if (i < n) {
             tile = src ? src[i] : i;
             kept = keep[i] != 0u;
-            const int w = width - (int)(tile % tiles_x) * 8, h = n_rows - (int)(tile / tiles_x) * 8;
-            px += (uint32_t)((w < 8 ? w : 8) * (h < 8 ? h : 8));
+            px += (uint32_t)grid.pixels_in(tile);
         }
         const uint64_t m = __ballot(kept);
-        if (lane == 0) s_cnt[wave] = count64(m);
+        if (lane == 0) s_cnt[wave] = wave_count(m);
         __syncthreads();
         uint32_t before = 0, total = 0;
 #pragma unroll
@@ -87,7 +77,7 @@ __global__ void __launch_bounds__(COMPACT_BLOCK) k_compact_order(const uint32_t*
             before += w < wave ? c : 0u;
             total += c;
         }
-        if (kept) dst[base + before + lanes_below(m)] = tile;   // < n: at most i tiles were kept before i
+        if (kept) dst[base + before + lane_rank(m)] = tile;   // < n: at most i tiles were kept before i
         base += total;
         __syncthreads();   // s_cnt is rewritten by the next chunk
     }

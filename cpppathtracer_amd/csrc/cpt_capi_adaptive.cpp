@@ -1,7 +1,7 @@
 // cpt_capi_adaptive.cpp — the C-ABI's adaptive render (include/cpt.h, DESIGN.md §Adaptive
 // sampling): rounds of `batch` passes over the 8x8 tiles that are still noisy, the noise map and
 // the round record, and the host-only hook on the criterion.  Each round is the launch cpt_render
-// makes (cpt_capi.cpp's helpers), over a shorter tile order; the kernels around it are
+// makes (cpt_capi_render.cpp's helpers), over a shorter tile order; the kernels around it are
 // cpt_adaptive.hip's.  The render is cpt_adaptive_begin (checks, buffers, the pilot, round 1
 // queued) and cpt_adaptive_step (one round's read-back, the next round queued), so that one thread
 // can keep a round queued on each of several contexts; cpt_render_adaptive is the two in a loop.
@@ -23,7 +23,7 @@ namespace {
 // behind it.  No host wait.
 int enqueue_round(cpt_ctx* c) {
     Frame& f = c->frame;
-    Frame::AdaptivePending& a = f.ad_pending;
+    AdaptiveState::Pending& a = f.adaptive.pending;
     hipStream_t s = c->stream();
     ++a.round;
     // round 1 is cpt_render's own launch (every tile, the caller's accumulate flag); later
@@ -39,17 +39,17 @@ int enqueue_round(cpt_ctx* c) {
     r.width = c->width;
     r.n_rows = c->n_rows;
     r.accum = f.d_accum;
-    r.snap = f.d_ad_snap;
-    r.stat = f.d_ad_stat;
-    r.keep = f.d_ad_keep;
+    r.snap = f.adaptive.d_snap;
+    r.stat = f.adaptive.d_stat;
+    r.keep = f.adaptive.d_keep;
     r.rel_error = a.rel_error;
     r.eligible = (long long)a.round * a.batch >= a.min_spp;
     r.last = a.round >= a.max_rounds;
     HIP_TRY(c, cpt::launch_tile_noise(r, s));
-    HIP_TRY(c, cpt::launch_compact_order(a.p.tile_order, f.d_ad_keep, a.active, c->width, c->n_rows, f.d_ad_order[a.into],
-                                         f.d_ad_count, s));
+    HIP_TRY(c, cpt::launch_compact_order(a.p.tile_order, f.adaptive.d_keep, a.active, c->width, c->n_rows, f.adaptive.d_order[a.into],
+                                         f.adaptive.d_count, s));
     uint32_t* h = c->h_ad_words.raw();
-    HIP_TRY(c, hipMemcpyAsync(h, f.d_ad_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(h, f.adaptive.d_count, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(h + 2, c->d_work + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipEventRecord(c->ev_round, s));
     a.queued = true;
@@ -74,19 +74,15 @@ int adaptive_begin(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, 
     if (flags & CPT_SCHEDULE_PREVIOUS)
         return fail(c, CPT_ERR_UNSUPPORTED, "%s: CPT_SCHEDULE_PREVIOUS (use CPT_SCHEDULE_COST)", who);
     Frame& f = c->frame;
-    if (f.ad_pending.on) return fail(c, CPT_ERR_STATE, "%s: an adaptive render is pending (cpt_adaptive_step until 0)", who);
-    if (!c->scene_set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_scene first", who);
-    if (!f.set || !f.rng_set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_frame + cpt_init_rng first", who);
-    if (cam->width != c->width || cam->height != c->height)
-        return fail(c, CPT_ERR_INVALID_ARG, "%s: camera %dx%d vs frame %dx%d", who, cam->width, cam->height, c->width,
-                    c->height);
+    if (f.adaptive.pending.on) return fail(c, CPT_ERR_STATE, "%s: an adaptive render is pending (cpt_adaptive_step until 0)", who);
+    if (int rc = renderable(c, cam, who)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream();
     const size_t npix = c->npix(), tiles = n_tiles(c);
-    f.ad_done = false;
-    f.ad_active.clear();
-    f.ad_passes = 0;
-    Frame::AdaptivePending a{};
+    f.adaptive.done = false;
+    f.adaptive.rounds.clear();
+    f.adaptive.passes = 0;
+    AdaptiveState::Pending a{};
     a.batch = batch;
     a.min_spp = min_spp;
     a.max_rounds = max_spp / batch;
@@ -94,7 +90,7 @@ int adaptive_begin(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, 
     a.active = (uint32_t)tiles;
     if (tiles == 0) {   // a context without rows: nothing to queue; the first step ends it
         a.on = true;
-        f.ad_pending = a;
+        f.adaptive.pending = a;
         return CPT_OK;
     }
     int rc;
@@ -104,40 +100,40 @@ int adaptive_begin(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, 
         if ((rc = f.d_normal.ensure(c, npix * 3)) != CPT_OK) return rc;
         if ((rc = f.d_depth.ensure(c, npix)) != CPT_OK) return rc;
     }
-    if ((rc = f.d_ad_snap.ensure(c, npix)) != CPT_OK || (rc = f.d_ad_stat.ensure(c, 4 * npix)) != CPT_OK ||
-        (rc = f.d_ad_keep.ensure(c, tiles)) != CPT_OK || (rc = f.d_ad_order[0].ensure(c, tiles)) != CPT_OK ||
-        (rc = f.d_ad_order[1].ensure(c, tiles)) != CPT_OK || (rc = f.d_ad_count.ensure(c, 2)) != CPT_OK)
+    if ((rc = f.adaptive.d_snap.ensure(c, npix)) != CPT_OK || (rc = f.adaptive.d_stat.ensure(c, 4 * npix)) != CPT_OK ||
+        (rc = f.adaptive.d_keep.ensure(c, tiles)) != CPT_OK || (rc = f.adaptive.d_order[0].ensure(c, tiles)) != CPT_OK ||
+        (rc = f.adaptive.d_order[1].ensure(c, tiles)) != CPT_OK || (rc = f.adaptive.d_count.ensure(c, 2)) != CPT_OK)
         return rc;
     // a new estimate: no batch seen; the snapshot is the accumulator the first round adds to
-    HIP_TRY(c, hipMemsetAsync(f.d_ad_stat, 0, 4 * npix * sizeof(float), s));
+    HIP_TRY(c, hipMemsetAsync(f.adaptive.d_stat, 0, 4 * npix * sizeof(float), s));
     if (flags & CPT_RENDER_ACCUMULATE)
-        HIP_TRY(c, hipMemcpyAsync(f.d_ad_snap, f.d_accum, npix * sizeof(float4), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(f.adaptive.d_snap, f.d_accum, npix * sizeof(float4), hipMemcpyDeviceToDevice, s));
     else
-        HIP_TRY(c, hipMemsetAsync(f.d_ad_snap, 0, npix * sizeof(float4), s));
+        HIP_TRY(c, hipMemsetAsync(f.adaptive.d_snap, 0, npix * sizeof(float4), s));
 
     fill_params(c, cam, batch, max_depth, flags, a.p);
-    c->have_timing = false;   // ev_start .. ev_stop span the rounds: no timing until the last step
-    HIP_TRY(c, hipEventRecord(c->ev_start, s));
+    c->t_render.recorded = false;   // ev_start .. ev_stop span the rounds: no timing until the last step
+    HIP_TRY(c, hipEventRecord(c->t_render.t0, s));
     if (flags & CPT_SCHEDULE_COST) {
         // one pilot, sized for the whole render; the rounds filter its order
         if ((rc = cost_pilot(c, a.p, cost_pilot_passes(max_spp), s)) != CPT_OK) return rc;
-        a.p.tile_order = f.d_tile_order;
+        a.p.tile_order = f.schedule.d_cost_order;
     }
     if ((rc = consolidation_slab(c, a.p, batch, flags)) != CPT_OK) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_main, s));
-    f.ad_pending = a;
+    f.adaptive.pending = a;
     if ((rc = enqueue_round(c)) != CPT_OK) {
-        f.ad_pending = Frame::AdaptivePending{};
+        f.adaptive.pending = AdaptiveState::Pending{};
         return rc;
     }
-    f.ad_pending.on = true;
+    f.adaptive.pending.on = true;
     return CPT_OK;
 }
 
 // The pending round's result, then the next round or the end of the render.
 int adaptive_step(cpt_ctx* c, int* active_tiles, const char* who) {
     Frame& f = c->frame;
-    Frame::AdaptivePending& a = f.ad_pending;
+    AdaptiveState::Pending& a = f.adaptive.pending;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream();
     if (a.queued) {
@@ -151,10 +147,10 @@ int adaptive_step(cpt_ctx* c, int* active_tiles, const char* who) {
             return rc != CPT_OK ? rc : fail(c, CPT_ERR_DEVICE, "%s: device error 0x%x", who, dev_err);
         }
         if (kept > a.active) return fail(c, CPT_ERR_DEVICE, "%s: %u of %u tiles kept", who, kept, a.active);
-        f.ad_active.push_back(a.active);
-        f.ad_passes += (uint64_t)pixels * (uint64_t)a.batch;
+        f.adaptive.rounds.push_back(a.active);
+        f.adaptive.passes += (uint64_t)pixels * (uint64_t)a.batch;
         a.active = kept;
-        a.p.tile_order = f.d_ad_order[a.into];
+        a.p.tile_order = f.adaptive.d_order[a.into];
         a.into ^= 1;
     }
     if (a.active > 0) {
@@ -163,14 +159,14 @@ int adaptive_step(cpt_ctx* c, int* active_tiles, const char* who) {
         return CPT_OK;
     }
     if (a.round > 0) {   // rounds ran (a context without rows has none, and no timing)
-        HIP_TRY(c, hipEventRecord(c->ev_stop, s));
+        HIP_TRY(c, hipEventRecord(c->t_render.t1, s));
         HIP_TRY(c, hipStreamSynchronize(s));
-        c->last_launches = (int)f.ad_active.size();
-        c->have_timing = true;
-        f.prev_d_valid = false;   // CPT_SCHEDULE_PREVIOUS counts draws from the next render on
+        c->last_launches = (int)f.adaptive.rounds.size();
+        c->t_render.recorded = true;
+        f.schedule.draws_moved();
     }
-    f.ad_pending = Frame::AdaptivePending{};
-    f.ad_done = true;
+    f.adaptive.pending = AdaptiveState::Pending{};
+    f.adaptive.done = true;
     *active_tiles = 0;
     return CPT_OK;
 }
@@ -178,11 +174,11 @@ int adaptive_step(cpt_ctx* c, int* active_tiles, const char* who) {
 // A failed step ends the render: nothing pending, no adaptive result; the stream is drained so
 // that what it still holds cannot run into the caller's next call.
 int adaptive_step_checked(cpt_ctx* c, int* active_tiles, const char* who) {
-    if (!c->frame.ad_pending.on) return fail(c, CPT_ERR_STATE, "%s: no adaptive render is pending (cpt_adaptive_begin first)", who);
+    if (!c->frame.adaptive.pending.on) return fail(c, CPT_ERR_STATE, "%s: no adaptive render is pending (cpt_adaptive_begin first)", who);
     const int rc = adaptive_step(c, active_tiles, who);
     if (rc != CPT_OK) {
-        c->frame.ad_pending = Frame::AdaptivePending{};
-        c->frame.ad_done = false;
+        c->frame.adaptive.pending = AdaptiveState::Pending{};
+        c->frame.adaptive.done = false;
         (void)hipStreamSynchronize(c->stream());
     }
     return rc;
@@ -213,22 +209,22 @@ int cpt_render_adaptive(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_
 
 int cpt_read_noise(cpt_ctx* c, float* rel, size_t capacity) {
     if (!c || !rel) return CPT_ERR_INVALID_ARG;
-    if (!c->frame.set || !c->frame.ad_done) return fail(c, CPT_ERR_STATE, "cpt_read_noise: cpt_render_adaptive first");
+    if (!c->frame.set || !c->frame.adaptive.done) return fail(c, CPT_ERR_STATE, "cpt_read_noise: cpt_render_adaptive first");
     const size_t n = c->npix();
     if (capacity < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_noise: %zu < %zu pixels", capacity, n);
     if (int rc = sync_checked(c)) return rc;
-    if (n) HIP_TRY(c, hipMemcpy(rel, c->frame.d_ad_stat + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(c, hipMemcpy(rel, c->frame.adaptive.d_stat + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost));
     return CPT_OK;
 }
 
 int cpt_adaptive_info(cpt_ctx* c, int* rounds, uint32_t* active_tiles_per_round, int capacity, uint64_t* passes_done) {
     if (!c || capacity < 0 || (capacity > 0 && !active_tiles_per_round)) return CPT_ERR_INVALID_ARG;
     const Frame& f = c->frame;
-    if (!f.set || !f.ad_done) return fail(c, CPT_ERR_STATE, "cpt_adaptive_info: cpt_render_adaptive first");
-    if (rounds) *rounds = (int)f.ad_active.size();
-    if (passes_done) *passes_done = f.ad_passes;
-    const size_t n = std::min((size_t)capacity, f.ad_active.size());
-    std::copy(f.ad_active.begin(), f.ad_active.begin() + n, active_tiles_per_round);
+    if (!f.set || !f.adaptive.done) return fail(c, CPT_ERR_STATE, "cpt_adaptive_info: cpt_render_adaptive first");
+    if (rounds) *rounds = (int)f.adaptive.rounds.size();
+    if (passes_done) *passes_done = f.adaptive.passes;
+    const size_t n = std::min((size_t)capacity, f.adaptive.rounds.size());
+    std::copy(f.adaptive.rounds.begin(), f.adaptive.rounds.begin() + n, active_tiles_per_round);
     return CPT_OK;
 }
 

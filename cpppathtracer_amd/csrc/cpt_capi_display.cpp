@@ -33,7 +33,7 @@ static int denoise_band(cpt_ctx* c, uint32_t cur_sample_idx, int y0, int y1, uin
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream();
     const size_t cap_rows = std::max<size_t>(out_rows, (size_t)(y1 - y0));
-    if (f.band_y0 != y0 || f.band_y1 != y1) {
+    if (f.display.y0 != y0 || f.display.y1 != y1) {
         // both new buffers first, then the switch: a failure here leaves the previous band, its
         // buffers and band_y0/1, as they were
         const size_t n = cap_rows * c->width;
@@ -43,10 +43,10 @@ static int denoise_band(cpt_ctx* c, uint32_t cur_sample_idx, int y0, int y1, uin
         if ((rc = mix.ensure(c, n * 3)) != CPT_OK || (rc = bgra.ensure(c, n * 4)) != CPT_OK) return rc;
         HIP_TRY(c, hipMemsetAsync(mix, 0, n * 3 * sizeof(float), s));
         HIP_TRY(c, hipMemsetAsync(bgra, 0, n * 4, s));
-        f.d_mix = std::move(mix);
-        f.d_bgra = std::move(bgra);
-        f.band_y0 = y0;
-        f.band_y1 = y1;
+        f.display.d_mix = std::move(mix);
+        f.display.d_bgra = std::move(bgra);
+        f.display.y0 = y0;
+        f.display.y1 = y1;
     }
     // A pinned host frame (hipHostMalloc / hipHostRegister, e.g. torch's pin_memory) is written by
     // the kernel itself through its device alias, so the PCIe transfer overlaps the stencil
@@ -60,19 +60,19 @@ static int denoise_band(cpt_ctx* c, uint32_t cur_sample_idx, int y0, int y1, uin
         else
             (void)hipGetLastError();   // pageable: not an error
     }
-    if (int rc = f.d_dn_sink.ensure(c, cpt::DN_SINK_SLOTS)) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_dn0, s));
-    HIP_TRY(c, cpt::launch_denoise_mix(f.d_accum, f.d_normal, f.d_depth, f.d_mix, f.d_bgra, host_alias, f.d_dn_sink, c->width,
+    if (int rc = f.display.d_sink.ensure(c, cpt::DN_SINK_SLOTS)) return rc;
+    HIP_TRY(c, hipEventRecord(c->t_display.t0, s));
+    HIP_TRY(c, cpt::launch_denoise_mix(f.d_accum, f.d_normal, f.d_depth, f.display.d_mix, f.display.d_bgra, host_alias, f.display.d_sink, c->width,
                                       c->height, row0, c->n_rows, y0, y1, cur_sample_idx, s));
-    HIP_TRY(c, hipEventRecord(c->ev_dn1, s));
-    c->have_dn_timing = true;
+    HIP_TRY(c, hipEventRecord(c->t_display.t1, s));
+    c->t_display.recorded = true;
     if (bgra_host && host_alias) {
         // the kernel writes the band's rows; the rest of the frame is zero, as the copy gives
         const size_t band = (size_t)(y1 - y0) * c->width * 4;
         std::memset(bgra_host + band, 0, cap_rows * c->width * 4 - band);
         HIP_TRY(c, hipStreamSynchronize(s));
     } else if (bgra_host) {
-        HIP_TRY(c, hipMemcpyAsync(bgra_host, f.d_bgra, cap_rows * c->width * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(bgra_host, f.display.d_bgra, cap_rows * c->width * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipStreamSynchronize(s));
     }
     return CPT_OK;
@@ -82,10 +82,10 @@ extern "C" {
 
 int cpt_last_display_ms(cpt_ctx* c, float* ms) {
     if (!c || !ms) return CPT_ERR_INVALID_ARG;
-    if (!c->have_dn_timing) return fail(c, CPT_ERR_STATE, "cpt_last_display_ms: no display frame yet");
+    if (!c->t_display.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_display_ms: no display frame yet");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->ev_dn1));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->ev_dn0, c->ev_dn1));
+    HIP_TRY(c, hipEventSynchronize(c->t_display.t1));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->t_display.t0, c->t_display.t1));
     return CPT_OK;
 }
 
@@ -125,29 +125,29 @@ int cpt_denoise_mix_band(cpt_ctx* c, uint32_t cur_sample_idx, int y0, int y1, ui
 int cpt_copy_bgra_device(cpt_ctx* c, void* device_dst, size_t bytes, void* caller_stream) {
     if (!c || !device_dst) return CPT_ERR_INVALID_ARG;
     const Frame& f = c->frame;
-    if (!f.d_bgra) return fail(c, CPT_ERR_STATE, "cpt_copy_bgra_device: no display frame yet");
-    const size_t have = (size_t)(f.band_y1 - f.band_y0) * c->width * 4;
+    if (!f.display.d_bgra) return fail(c, CPT_ERR_STATE, "cpt_copy_bgra_device: no display frame yet");
+    const size_t have = (size_t)(f.display.y1 - f.display.y0) * c->width * 4;
     if (bytes > have) return fail(c, CPT_ERR_INVALID_ARG, "cpt_copy_bgra_device: %zu bytes requested, band holds %zu", bytes, have);
-    return copy_ordered(c, device_dst, f.d_bgra, bytes, (hipStream_t)caller_stream);
+    return copy_ordered(c, device_dst, f.display.d_bgra, bytes, (hipStream_t)caller_stream);
 }
 
 int cpt_display_band(const cpt_ctx* c, int* y0, int* y1) {
     if (!c || !y0 || !y1) return CPT_ERR_INVALID_ARG;
-    *y0 = c->frame.d_mix ? c->frame.band_y0 : 0;
-    *y1 = c->frame.d_mix ? c->frame.band_y1 : 0;
+    *y0 = c->frame.display.d_mix ? c->frame.display.y0 : 0;
+    *y1 = c->frame.display.d_mix ? c->frame.display.y1 : 0;
     return CPT_OK;
 }
 
 int cpt_read_mix(cpt_ctx* c, float* rgb, size_t capacity) {
     if (!c || !rgb) return CPT_ERR_INVALID_ARG;
     const Frame& f = c->frame;
-    if (!f.d_mix) return fail(c, CPT_ERR_STATE, "cpt_read_mix: no display frame yet");
-    const size_t rows = (size_t)(f.band_y1 - f.band_y0);
+    if (!f.display.d_mix) return fail(c, CPT_ERR_STATE, "cpt_read_mix: no display frame yet");
+    const size_t rows = (size_t)(f.display.y1 - f.display.y0);
     if (capacity < rows * c->width * 3)
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_mix: %zu floats given, the band [%d, %d) holds %zu", capacity,
-                    f.band_y0, f.band_y1, rows * c->width * 3);
+                    f.display.y0, f.display.y1, rows * c->width * 3);
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(rgb, f.d_mix, rows * c->width * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream()));
+    HIP_TRY(c, hipMemcpyAsync(rgb, f.display.d_mix, rows * c->width * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream()));
     return sync_checked(c);
 }
 
@@ -155,10 +155,10 @@ int cpt_reset_display(cpt_ctx* c) {
     if (!c) return CPT_ERR_INVALID_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     const Frame& f = c->frame;
-    if (f.d_mix) {
+    if (f.display.d_mix) {
         const int h_eff = 16 * (c->height / 16);
-        const size_t rows = f.band_y0 == 0 && f.band_y1 == h_eff ? (size_t)c->height : (size_t)(f.band_y1 - f.band_y0);
-        HIP_TRY(c, hipMemsetAsync(f.d_mix, 0, rows * c->width * 3 * sizeof(float), c->stream()));
+        const size_t rows = f.display.y0 == 0 && f.display.y1 == h_eff ? (size_t)c->height : (size_t)(f.display.y1 - f.display.y0);
+        HIP_TRY(c, hipMemsetAsync(f.display.d_mix, 0, rows * c->width * 3 * sizeof(float), c->stream()));
     }
     return CPT_OK;
 }

@@ -34,37 +34,37 @@ int cpt_filter_frame(cpt_ctx* c, int levels, float sigma_l, int normal_sharpness
     for (int y = 0; y < c->height; ++y)
         if (c->rows_h[y] != y) return fail(c, CPT_ERR_STATE, "cpt_filter_frame: needs rows 0..height-1 in order");
     const size_t npix = c->npix();
-    if (!f.ad_done || f.d_ad_stat.capacity() < 4 * npix)
+    if (!f.adaptive.has_result(npix))
         return fail(c, CPT_ERR_STATE, "cpt_filter_frame: no moments (cpt_render_adaptive or cpt_write_moments first)");
     if (f.d_normal.capacity() < 3 * npix)
         return fail(c, CPT_ERR_STATE, "cpt_filter_frame: no normals (render with CPT_RENDER_AUX or cpt_write_aux first)");
     HIP_TRY(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = f.d_flt[0].ensure(c, npix)) != CPT_OK || (rc = f.d_flt[1].ensure(c, npix)) != CPT_OK ||
-        (rc = f.d_flt_ok.ensure(c, npix)) != CPT_OK)
+    if ((rc = f.filter.d_plane[0].ensure(c, npix)) != CPT_OK || (rc = f.filter.d_plane[1].ensure(c, npix)) != CPT_OK ||
+        (rc = f.filter.d_ok.ensure(c, npix)) != CPT_OK)
         return rc;
-    f.flt_result = -1;
+    f.filter.result = -1;
     hipStream_t s = c->stream();
-    HIP_TRY(c, hipEventRecord(c->ev_flt0, s));
-    HIP_TRY(c, cpt::launch_filter_prepare(f.d_accum, f.d_ad_stat, npix, f.d_flt[0], f.d_flt_ok, s));
+    HIP_TRY(c, hipEventRecord(c->t_filter.t0, s));
+    HIP_TRY(c, cpt::launch_filter_prepare(f.d_accum, f.adaptive.d_stat, npix, f.filter.d_plane[0], f.filter.d_ok, s));
     for (int l = 0; l < levels; ++l)
-        HIP_TRY(c, cpt::launch_filter_level(f.d_flt[l & 1], f.d_normal, f.d_flt_ok, f.d_flt[(l + 1) & 1], c->width, c->height,
+        HIP_TRY(c, cpt::launch_filter_level(f.filter.d_plane[l & 1], f.d_normal, f.filter.d_ok, f.filter.d_plane[(l + 1) & 1], c->width, c->height,
                                            1 << l, sigma_l * sigma_l, normal_sharpness_log2, s));
-    HIP_TRY(c, hipEventRecord(c->ev_flt1, s));
-    c->have_flt_timing = true;
-    f.flt_result = levels & 1;
+    HIP_TRY(c, hipEventRecord(c->t_filter.t1, s));
+    c->t_filter.recorded = true;
+    f.filter.result = levels & 1;
     return CPT_OK;
 }
 
 int cpt_read_filtered(cpt_ctx* c, float* rgb, float* variance, size_t capacity_pixels) {
     if (!c) return CPT_ERR_INVALID_ARG;
     const Frame& f = c->frame;
-    if (!f.set || f.flt_result < 0) return fail(c, CPT_ERR_STATE, "cpt_read_filtered: cpt_filter_frame first");
+    if (!f.set || f.filter.result < 0) return fail(c, CPT_ERR_STATE, "cpt_read_filtered: cpt_filter_frame first");
     const size_t n = c->npix();
     if (capacity_pixels < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_filtered: %zu < %zu pixels", capacity_pixels, n);
     if (int rc = sync_checked(c)) return rc;
     std::vector<float> plane(4 * n);
-    HIP_TRY(c, hipMemcpy(plane.data(), f.d_flt[f.flt_result], n * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(plane.data(), f.filter.d_plane[f.filter.result], n * sizeof(float4), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) {
         if (rgb) {
             rgb[3 * i] = plane[4 * i];
@@ -78,21 +78,21 @@ int cpt_read_filtered(cpt_ctx* c, float* rgb, float* variance, size_t capacity_p
 
 int cpt_last_filter_ms(cpt_ctx* c, float* ms) {
     if (!c || !ms) return CPT_ERR_INVALID_ARG;
-    if (!c->have_flt_timing) return fail(c, CPT_ERR_STATE, "cpt_last_filter_ms: no cpt_filter_frame yet");
+    if (!c->t_filter.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_filter_ms: no cpt_filter_frame yet");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->ev_flt1));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->ev_flt0, c->ev_flt1));
+    HIP_TRY(c, hipEventSynchronize(c->t_filter.t1));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->t_filter.t0, c->t_filter.t1));
     return CPT_OK;
 }
 
 int cpt_read_moments(cpt_ctx* c, float* planar4, size_t capacity) {
     if (!c || !planar4) return CPT_ERR_INVALID_ARG;
     const Frame& f = c->frame;
-    if (!f.set || !f.ad_done) return fail(c, CPT_ERR_STATE, "cpt_read_moments: cpt_render_adaptive or cpt_write_moments first");
+    if (!f.set || !f.adaptive.done) return fail(c, CPT_ERR_STATE, "cpt_read_moments: cpt_render_adaptive or cpt_write_moments first");
     const size_t n = 4 * c->npix();
     if (capacity < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_moments: %zu < %zu floats", capacity, n);
     if (int rc = sync_checked(c)) return rc;
-    if (n) HIP_TRY(c, hipMemcpy(planar4, f.d_ad_stat, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(c, hipMemcpy(planar4, f.adaptive.d_stat, n * sizeof(float), hipMemcpyDeviceToHost));
     return CPT_OK;
 }
 
@@ -104,12 +104,9 @@ int cpt_write_moments(cpt_ctx* c, const float* planar4, size_t count) {
     if (count < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_write_moments: %zu < %zu floats", count, n);
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream()));
-    if (int rc = f.d_ad_stat.ensure(c, n)) return rc;
-    if (n) HIP_TRY(c, hipMemcpy(f.d_ad_stat, planar4, n * sizeof(float), hipMemcpyHostToDevice));
-    // an adaptive result that no round of this context produced: an empty round record
-    f.ad_active.clear();
-    f.ad_passes = 0;
-    f.ad_done = true;
+    if (int rc = f.adaptive.d_stat.ensure(c, n)) return rc;
+    if (n) HIP_TRY(c, hipMemcpy(f.adaptive.d_stat, planar4, n * sizeof(float), hipMemcpyHostToDevice));
+    f.adaptive.adopt_result();
     return CPT_OK;
 }
 

@@ -54,9 +54,9 @@ int cpt_gather_rows(cpt_ctx* dst, cpt_ctx* src) {
         return fail(dst, CPT_ERR_INVALID_ARG, "cpt_gather_rows: frame %dx%d vs %dx%d", dst->width, dst->height, src->width,
                     src->height);
     // a pending adaptive render's rounds still write src's buffers (and would write dst's)
-    if (src->frame.ad_pending.on || dst->frame.ad_pending.on)
+    if (src->frame.adaptive.pending.on || dst->frame.adaptive.pending.on)
         return fail(dst, CPT_ERR_STATE, "cpt_gather_rows: an adaptive render is pending on the %s (cpt_adaptive_step until 0)",
-                    src->frame.ad_pending.on ? "source" : "destination");
+                    src->frame.adaptive.pending.on ? "source" : "destination");
     cpt_ctx::GatherMap* gm = nullptr;
     for (auto& g : dst->gather_maps)
         if (g.src == src) gm = &g;
@@ -95,7 +95,7 @@ int cpt_gather_rows(cpt_ctx* dst, cpt_ctx* src) {
     Frame &sf = src->frame, &df = dst->frame;
     const bool aux = sf.d_normal && sf.d_depth;
     // an adaptive result on src: its moment planes travel with its rows
-    const bool moments = sf.ad_done && sf.d_ad_stat.capacity() >= 4 * npix;
+    const bool moments = sf.adaptive.has_result(npix);
     // src's queued work (its render) before the stitch
     HIP_TRY(src, hipSetDevice(src->device));
     HIP_TRY(src, hipEventRecord(src->ev_ready, src->stream()));
@@ -117,21 +117,18 @@ int cpt_gather_rows(cpt_ctx* dst, cpt_ctx* src) {
     if (moments) {
         // a destination without an adaptive result of its own starts as pixels before their second
         // batch: m1 = m2 = k = 0 (invalid for the filter) and +inf noise, where no source covers a row
-        const bool fresh = !df.ad_done || df.d_ad_stat.capacity() < 4 * dst_npix;
-        if (int rc = df.d_ad_stat.ensure(dst, 4 * dst_npix)) return rc;
+        const bool fresh = !df.adaptive.has_result(dst_npix);
+        if (int rc = df.adaptive.d_stat.ensure(dst, 4 * dst_npix)) return rc;
         if (fresh) {
-            HIP_TRY(dst, hipMemsetAsync(df.d_ad_stat, 0, 3 * dst_npix * sizeof(float), s));
-            HIP_TRY(dst, hipMemsetD32Async((hipDeviceptr_t)(df.d_ad_stat + 3 * dst_npix), 0x7f800000, dst_npix, s));
+            HIP_TRY(dst, hipMemsetAsync(df.adaptive.d_stat, 0, 3 * dst_npix * sizeof(float), s));
+            HIP_TRY(dst, hipMemsetD32Async((hipDeviceptr_t)(df.adaptive.d_stat + 3 * dst_npix), 0x7f800000, dst_npix, s));
         }
-        // as cpt_write_moments: a result that no round of this context produced
-        df.ad_active.clear();
-        df.ad_passes = 0;
-        df.ad_done = true;
+        df.adaptive.adopt_result();
     }
     const float4* s_acc = sf.d_accum;
     const float* s_nrm = aux ? sf.d_normal.get() : nullptr;
     const float* s_dep = aux ? sf.d_depth.get() : nullptr;
-    const float* s_stat = moments ? sf.d_ad_stat.get() : nullptr;
+    const float* s_stat = moments ? sf.adaptive.d_stat.get() : nullptr;
     if (staged) {
         // staging: accumulator (npix float4), then normals (3 npix floats) and depths (npix floats)
         if (int rc = dst->d_gather.ensure(dst, aux ? 2 * npix : npix)) return rc;
@@ -148,7 +145,7 @@ int cpt_gather_rows(cpt_ctx* dst, cpt_ctx* src) {
         if (moments) {
             // a staging buffer of their own: the layout above is that of a source without moments
             if (int rc = dst->d_gather_stat.ensure(dst, 4 * npix)) return rc;
-            HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_gather_stat, dst->device, sf.d_ad_stat, src->device,
+            HIP_TRY(dst, hipMemcpyPeerAsync(dst->d_gather_stat, dst->device, sf.adaptive.d_stat, src->device,
                                             4 * npix * sizeof(float), s));
             s_stat = dst->d_gather_stat;
         }
@@ -156,7 +153,7 @@ int cpt_gather_rows(cpt_ctx* dst, cpt_ctx* src) {
     HIP_TRY(dst, cpt::launch_stitch_rows(s_acc, s_nrm, s_dep, gm->d_map, dst->width, src->n_rows, df.d_accum,
                                          df.d_normal, df.d_depth, s));
     if (moments)
-        HIP_TRY(dst, cpt::launch_stitch_moments(s_stat, npix, gm->d_map, dst->width, src->n_rows, df.d_ad_stat, dst_npix, s));
+        HIP_TRY(dst, cpt::launch_stitch_moments(s_stat, npix, gm->d_map, dst->width, src->n_rows, df.adaptive.d_stat, dst_npix, s));
     // src's later work (a next render into the buffers just read) after the stitch
     HIP_TRY(dst, hipEventRecord(dst->ev_gathered, s));
     HIP_TRY(src, hipSetDevice(src->device));

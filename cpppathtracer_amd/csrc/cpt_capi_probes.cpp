@@ -59,16 +59,16 @@ int cpt_debug_read_tile_order(cpt_ctx* c, int which, uint32_t* out, size_t capac
     const uint32_t* src = nullptr;   // stays null for the pending round's list without an order: 0, 1, 2, ...
     size_t len = n_tiles(c);
     if (which == 0) {
-        if (!f.set || !f.d_tile_order) return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no cost pilot on this frame");
-        src = f.d_tile_order;
+        if (!f.set || !f.schedule.d_cost_order) return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no cost pilot on this frame");
+        src = f.schedule.d_cost_order;
     } else if (which == 1) {
-        if (!f.set || !f.prev_order_valid)
+        src = f.schedule.previous_order();
+        if (!f.set || !src)
             return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no CPT_SCHEDULE_PREVIOUS order on this frame");
-        src = f.d_prev_order;
     } else {
-        if (!f.ad_pending.on) return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no adaptive render is pending");
-        src = f.ad_pending.p.tile_order;
-        len = f.ad_pending.active;
+        if (!f.adaptive.pending.on) return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no adaptive render is pending");
+        src = f.adaptive.pending.p.tile_order;
+        len = f.adaptive.pending.active;
     }
     *n = len;
     if (capacity < len) return fail(c, CPT_ERR_INVALID_ARG, "cpt_debug_read_tile_order: %zu < %zu tiles", capacity, len);

@@ -1,9 +1,9 @@
 // cpt_context.hpp — the C-ABI's context (struct cpt_ctx of include/cpt.h) and the helpers its
-// implementation files share: cpt_capi.cpp (context, frame, RNG, render, accumulator, counters),
-// cpt_capi_adaptive.cpp (adaptive render), cpt_capi_filter.cpp (a-trous filter), cpt_capi_gather.cpp (row-tile gather),
+// implementation files share: cpt_capi.cpp (context, frame, RNG, accumulator, counters),
+// cpt_capi_render.cpp (render launches, tile schedules, timing), cpt_capi_adaptive.cpp (adaptive
+// render), cpt_capi_filter.cpp (a-trous filter), cpt_capi_gather.cpp (row-tile gather),
 // cpt_capi_display.cpp (display path), cpt_capi_probes.cpp (diagnostic probes, self-tests) and
-// cpt_scene.cpp (scene upload, material slots, walk trees,
-// device refit).  Host code only.
+// cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "cpt_devmem.hpp"
 #include "cpt_host.hpp"
 #include "cpt_internal.hpp"
+#include "cpt_tiles.hpp"
 
 using cpt::Mat;
 using cpt::Node;
@@ -28,47 +29,75 @@ using cpt::host::HostBvh;
 struct WfStorage {
     std::vector<DevBuf<uint8_t>> mem;   // 12 float4 + 4 RNG + 3 queue arrays and the counts
     // All arrays for `npix` pixels and the view of them, or nothing: a failed allocation
-    // part-way leaves both as they were (cpt_capi.cpp, the one list of the arrays).
+    // part-way leaves both as they were (cpt_capi_render.cpp, the one list of the arrays).
     int alloc(cpt_ctx* c, size_t npix, cpt::WfState& view);
 };
 
-// Everything that lives and dies with cpt_set_frame (which assigns a fresh Frame): the device
-// buffers sized by the frame and the flags that say what they hold.
-struct Frame {
-    bool set = false, rng_set = false;
-    DevBuf<int32_t> d_rows;
-    DevBuf<uint32_t> d_rng;
-    DevBuf<float4> d_accum;
-    DevBuf<float> d_normal, d_depth;
-    // rng init (released again once the states are written)
-    DevBuf<uint32_t> d_scratch_w, d_scratch_m;
-    DevBuf<uint8_t> d_sched;     // cost schedule: pilot tile costs + sort scratch (bytes)
-    DevBuf<uint32_t> d_tile_order;
-    // CPT_SCHEDULE_PREVIOUS: the Weyl plane after the last such render, and the tile order
-    // its draws gave (the next render's dequeue order)
+// What lives and dies with cpt_set_frame (which assigns a fresh Frame), by subsystem: each owns its
+// device buffers, sized by the frame and allocated on first use, and the flags that say what they hold.
+
+// The tile orders of CPT_SCHEDULE_COST and CPT_SCHEDULE_PREVIOUS (cpt_capi_render.cpp).
+struct TileSchedule {
+    DevBuf<uint8_t> d_scratch;       // pilot tile costs + sort scratch (bytes), shared by both orders
+    DevBuf<uint32_t> d_cost_order;   // the cost pilot's order (cost_pilot)
+    // CPT_SCHEDULE_PREVIOUS: the Weyl plane the draws are counted from, and the tile order the
+    // draws up to the last rebuild gave (the next such render's dequeue order)
     DevBuf<uint32_t> d_prev_d, d_prev_order;
+
+    // The RNG streams were replaced (cpt_init_rng): the order was measured on streams that are
+    // gone, and so was the plane.  The next CPT_SCHEDULE_PREVIOUS render runs in raster order,
+    // counts its draws from its start and rebuilds the order.
+    void rng_replaced() {
+        prev_d_valid = prev_order_valid = false;
+        prev_since_order = 0;
+    }
+    // Draws happened, or the states changed, outside a CPT_SCHEDULE_PREVIOUS render (cpt_write_rng,
+    // an adaptive render): the plane no longer matches, so the next such render counts from its
+    // start.  The order stays valid, and its rebuild is not brought forward: it is a heuristic for
+    // the dequeue order only, the image does not depend on it, and a caller who writes back states
+    // it read (a checkpoint) keeps the order that fits them.
+    void draws_moved() { prev_d_valid = false; }
+    // The CPT_SCHEDULE_PREVIOUS order, or null while none is valid.
+    const uint32_t* previous_order() const { return prev_order_valid ? d_prev_order.get() : nullptr; }
+    // Around a CPT_SCHEDULE_PREVIOUS render: the order to dequeue in and the plane to count from;
+    // then, every PREV_ORDER_EVERY renders, the order rebuilt from the draws since.
+    int previous_begin(cpt_ctx* c, cpt::KParams& p, hipStream_t s);
+    int previous_refresh(cpt_ctx* c, const cpt::KParams& p, hipStream_t s);
+
+private:
     bool prev_d_valid = false, prev_order_valid = false;
-    int prev_since_order = 0;   // renders since the CPT_SCHEDULE_PREVIOUS order was rebuilt
-    cpt::WfState wf{};           // wavefront path state (allocated on first use)
-    WfStorage wf_mem;
-    bool wf_ready = false;
-    DevBuf<float> d_mix;         // display running mean (Mix), rgb per pixel of the display band
-    DevBuf<uint8_t> d_bgra;      // display frame (band rows)
-    DevBuf<float4> d_dn_sink;    // k_denoise_strip: where lanes without an output pixel store (DN_SINK_SLOTS)
-    int band_y0 = -1, band_y1 = -1;   // display band the buffers hold
-    // adaptive render (cpt_capi_adaptive.cpp; allocated on the frame's first cpt_render_adaptive):
+    int prev_since_order = 0;   // renders since the order was rebuilt
+};
+
+// The wavefront path (allocated on the frame's first wavefront render).
+struct WavefrontState {
+    cpt::WfState view{};
+    WfStorage mem;
+    bool ready = false;   // allocated, the identity queue built
+};
+
+// The display path (cpt_capi_display.cpp): the buffers of one band of output rows.
+struct DisplayBand {
+    DevBuf<float> d_mix;       // running mean (Mix), rgb per pixel of the band
+    DevBuf<uint8_t> d_bgra;    // the display frame (band rows)
+    DevBuf<float4> d_sink;     // k_denoise_strip: where lanes without an output pixel store (DN_SINK_SLOTS)
+    int y0 = -1, y1 = -1;      // the band the buffers hold
+};
+
+// The adaptive render (cpt_capi_adaptive.cpp; allocated on the frame's first cpt_render_adaptive).
+struct AdaptiveState {
     // the accumulator before the current round, the per-pixel moments and noise map (planar
     // [4][npix]: m1, m2, k, rel), a keep flag per position of the active list, the list's two
     // buffers (each round compacts one into the other) and {new length, pixels rendered}
-    DevBuf<float4> d_ad_snap;
-    DevBuf<float> d_ad_stat;
-    DevBuf<uint32_t> d_ad_keep, d_ad_order[2], d_ad_count;
-    bool ad_done = false;                  // an adaptive render has completed on this frame
-    std::vector<uint32_t> ad_active;       // its rounds: the tiles each one rendered
-    uint64_t ad_passes = 0;                // its pixel passes, all rounds
-    // an adaptive render between cpt_adaptive_begin and the cpt_adaptive_step that returns 0: what
-    // the next round is launched with; `queued`: a round and its read-back are on the stream
-    struct AdaptivePending {
+    DevBuf<float4> d_snap;
+    DevBuf<float> d_stat;
+    DevBuf<uint32_t> d_keep, d_order[2], d_count;
+    bool done = false;               // d_stat holds a result (a completed render's, or an adopted one)
+    std::vector<uint32_t> rounds;    // the render's rounds: the tiles each one rendered
+    uint64_t passes = 0;             // its pixel passes, all rounds
+    // a render between cpt_adaptive_begin and the cpt_adaptive_step that returns 0: what the next
+    // round is launched with; `queued`: a round and its read-back are on the stream
+    struct Pending {
         bool on = false, queued = false;
         cpt::KParams p{};
         bool stats = false, aux = false;
@@ -77,13 +106,45 @@ struct Frame {
         int round = 0;          // rounds queued so far
         uint32_t active = 0;    // tiles of the round queued (or to queue) next
         int into = 0;           // the order buffer the next compaction writes
-    } ad_pending;
-    // a-trous filter (cpt_capi_filter.cpp; allocated on the frame's first cpt_filter_frame): the two
-    // planes the levels ping-pong between (rgb + variance of the mean), each pixel's validity, and
-    // the plane that holds the last call's result (-1: no call yet)
-    DevBuf<float4> d_flt[2];
-    DevBuf<uint8_t> d_flt_ok;
-    int flt_result = -1;
+    } pending;
+
+    // moments of `npix` pixels that the filter and the gather can read
+    bool has_result(size_t npix) const { return done && d_stat.capacity() >= 4 * npix; }
+    // d_stat was filled from outside (cpt_write_moments, a gather): a result that no round of
+    // this context produced, with an empty round record
+    void adopt_result() {
+        rounds.clear();
+        passes = 0;
+        done = true;
+    }
+};
+
+// The a-trous filter (cpt_capi_filter.cpp; allocated on the frame's first cpt_filter_frame).
+struct FilterState {
+    DevBuf<float4> d_plane[2];   // the levels ping-pong between them (rgb + variance of the mean)
+    DevBuf<uint8_t> d_ok;        // each pixel's validity
+    int result = -1;             // the plane that holds the last call's result (-1: no call yet)
+};
+
+struct Frame {
+    bool set = false, rng_set = false;
+    DevBuf<int32_t> d_rows;
+    DevBuf<uint32_t> d_rng;
+    DevBuf<float4> d_accum;
+    DevBuf<float> d_normal, d_depth;
+    // rng init (released again once the states are written)
+    DevBuf<uint32_t> d_scratch_w, d_scratch_m;
+    TileSchedule schedule;
+    WavefrontState wavefront;
+    DisplayBand display;
+    AdaptiveState adaptive;
+    FilterState filter;
+};
+
+// A pair of timing events around a subsystem's last launches, once they have been recorded.
+struct TimedSpan {
+    DevEvent t0, t1;
+    bool recorded = false;
 };
 
 // ======================================================================================
@@ -95,13 +156,10 @@ struct cpt_ctx {
     // declared before the buffers and events: destroyed after them
     cpt::ctx::DevStream own_stream;
     hipStream_t user_stream = nullptr;
-    DevEvent ev_start, ev_stop;
-    DevEvent ev_main;   // after the cost schedule's pilot: the dominant kernel(s) only
-    bool have_timing = false;
-    DevEvent ev_dn0, ev_dn1;   // around the last display kernel (k_denoise_rows)
-    bool have_dn_timing = false;
-    DevEvent ev_flt0, ev_flt1;   // around the last cpt_filter_frame's launches
-    bool have_flt_timing = false;
+    TimedSpan t_render;    // the last render, all of it
+    DevEvent ev_main;      // after the cost schedule's pilot: the dominant kernel(s) only, to t_render.t1
+    TimedSpan t_display;   // the last display kernel (k_denoise_rows)
+    TimedSpan t_filter;    // the last cpt_filter_frame's launches
     std::string err;
 
     // scene
@@ -195,7 +253,7 @@ namespace ctx {
 // cpt_adaptive_begin and the cpt_adaptive_step that returns 0): its rounds own the frame's buffers.
 #define CPT_REFUSE_PENDING(ctx, who)                                                                              \
     do {                                                                                                          \
-        if ((ctx)->frame.ad_pending.on)                                                                           \
+        if ((ctx)->frame.adaptive.pending.on)                                                                           \
             return fail((ctx), CPT_ERR_STATE, who ": an adaptive render is pending (cpt_adaptive_step until 0)"); \
     } while (0)
 
@@ -205,9 +263,13 @@ int sync_checked(cpt_ctx* c);
 // A device-to-device copy from one of the context's buffers, ordered against the caller's
 // stream without a host wait (cpt_capi.cpp).
 int copy_ordered(cpt_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t caller);
-// What a megakernel launch of the context's frame is made of (cpt_capi.cpp; shared with
+// What cpt_render, cpt_tile_costs and cpt_adaptive_begin ask before they launch, in this order:
+// a scene, a frame with RNG states, a camera of the frame's size (the messages start with `who`).
+// max_depth (0..32) each of them checks with its own arguments, before this.
+int renderable(cpt_ctx* c, const cpt_camera* cam, const char* who);
+// What a megakernel launch of the context's frame is made of (cpt_capi_render.cpp; shared with
 // cpt_capi_adaptive.cpp): the kernel parameters, the frame's 8x8 tiles, the cost schedule's pilot
-// into Frame::d_tile_order and its length for a render of `spp` passes, the consolidation slab.
+// into TileSchedule::d_cost_order and its length for a render of `spp` passes, the consolidation slab.
 void fill_params(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32_t flags, cpt::KParams& p);
 size_t n_tiles(const cpt_ctx* c);
 int cost_pilot_passes(int spp);

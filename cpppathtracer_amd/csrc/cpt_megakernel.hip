@@ -2,8 +2,8 @@
 //
 //   k_megakernel         SamplePixel (path_tracer.cu:124-175), all spp passes per launch,
 //                        per-lane path regeneration, state in registers; with what it alone
-//                        uses: Lane, decode_pixel, the coherent load/store helpers, ho_slots,
-//                        lane_rank, and the hand-over queue of the tail consolidation
+//                        uses: Lane, decode_pixel, the coherent load/store helpers, ho_slots
+//                        and the hand-over queue of the tail consolidation
 //   launch_mk*           the persistent grid and the STATS / AUX / PROBE / LDS / CONS / HYB ladder
 //   launch_megakernel    the render's entry;  launch_cost_pilot: the cost schedule's pilot
 //   timeline_read        the CPT_TIMELINE read-out (timeline::g_tl is per translation unit)
@@ -65,9 +65,6 @@ __device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)
 // Hand-over slots per workgroup: each of the waves of levels 1.. retires once and hands over
 // at most its 64 chains, so (levels - 1) x 256 slots always suffice.
 template <int BLK> constexpr int ho_slots() { return (BLK / 256 - 1) * 256; }
-__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {   // set lanes of `mask` below this one
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
 
 struct Lane {
     uint32_t xy;     // x | y << 16 (frames are < 65536 pixels wide and high)
@@ -117,13 +114,9 @@ struct PendingSky {
 };
 
 __device__ __forceinline__ bool decode_pixel(const KParams& p, uint32_t id, int& x, int& ri, uint32_t& tile) {
-    const int tiles_x = (p.width + 7) >> 3;
     tile = id >> 6;
     if (p.tile_order) tile = p.tile_order[tile];
-    const uint32_t k = id & 63;
-    x = (int)(tile % tiles_x) * 8 + (int)(k & 7);
-    ri = (int)(tile / tiles_x) * 8 + (int)(k >> 3);
-    return x < p.width && ri < p.n_rows;
+    return TileGrid{p.width, p.n_rows}.pixel(tile, id & 63, x, ri);
 }
 
 // Scheduling constants (SUSPEND_AT, STATIC_FIRST, DEFER_MISS_ROUND, CPT_LDS_BLOCK): cpt_tuning.hpp.
@@ -153,7 +146,7 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
     const int lane = threadIdx.x & 63;
     const size_t npix = (size_t)p.n_rows * p.width;
     // (an adaptive render's later rounds dequeue only the first n_active tiles of p.tile_order)
-    const uint32_t n_work = (p.n_active ? p.n_active : (uint32_t)(((p.width + 7) >> 3) * ((p.n_rows + 7) >> 3))) * 64u;
+    const uint32_t n_work = (p.n_active ? p.n_active : (uint32_t)TileGrid{p.width, p.n_rows}.count()) * 64u;
     const uint32_t max_depth = (uint32_t)p.max_depth;
     Counters cnt{};
     uint32_t work_at_take = 0;   // PROBE: the lane's counters when it took its pixel
@@ -643,7 +636,7 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
 }
 
 // ======================================================================================
-// Host-side launchers (called from cpt_capi.cpp).
+// Host-side launchers (called from cpt_capi_render.cpp and cpt_capi_adaptive.cpp).
 // ======================================================================================
 template <bool S, bool A, bool P, bool T, bool C = false, bool H = false>
 static hipError_t launch_mk(const KParams& p, int max_workgroups, hipStream_t stream) {
@@ -659,7 +652,7 @@ static hipError_t launch_mk(const KParams& p, int max_workgroups, hipStream_t st
         if (blocks_per_cu < 1) blocks_per_cu = 1;
     }
     // persistent grid: every resident slot once; lanes pull pixels from p.work
-    const long long tiles = p.n_active ? (long long)p.n_active : (long long)((p.width + 7) / 8) * ((p.n_rows + 7) / 8);
+    const long long tiles = p.n_active ? (long long)p.n_active : (long long)TileGrid{p.width, p.n_rows}.count();
     // a wave holds p.lanes / p.replicate pixels at once (64 in normal use; fewer: DIAGNOSTIC)
     const int per_wave = std::max(1, p.lanes / std::max(1, p.replicate));
     long long want = (tiles * 64 * ((64 + per_wave - 1) / per_wave) + block - 1) / block;

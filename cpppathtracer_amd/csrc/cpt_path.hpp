@@ -9,6 +9,7 @@
 #include "cpt_device.hpp"
 #include "cpt_internal.hpp"
 #include "cpt_stamps.hpp"
+#include "cpt_tiles.hpp"
 #include "cpt_tuning.hpp"
 
 namespace cpt {
@@ -655,13 +656,6 @@ __device__ __forceinline__ int trace(const SRC& nodes, int n_nodes, const RayK& 
 // never below the final tmax; the rank rule and the certificate are unchanged.
 // ======================================================================================
 constexpr int WIDE_LANES = 256;   // block size of the kernels without the LDS image
-
-// Number of set bits of a wave-uniform mask as a 32-bit value (two 32-bit popcounts: the
-// compiler then compares it with SALU s_cmp_*_u32; a 64-bit popcount it compares with VALU
-// v_cmp_*_u64).  (Not inline asm: s_bcnt1 writes SCC, which an asm statement cannot declare.)
-__device__ __forceinline__ uint32_t wave_count(uint64_t m) {
-    return (uint32_t)__builtin_popcount((uint32_t)m) + (uint32_t)__builtin_popcount((uint32_t)(m >> 32));
-}
 
 typedef __attribute__((address_space(3))) int16_t lds_i16;
 

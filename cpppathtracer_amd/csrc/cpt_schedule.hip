@@ -28,15 +28,15 @@ __global__ void k_iota(uint32_t* v, uint32_t n) {
 }
 
 size_t tile_schedule_scratch_bytes(int width, int n_rows) {
-    const int n = ((width + 7) / 8) * ((n_rows + 7) / 8);
+    const int n = TileGrid{width, n_rows}.count();
     size_t temp = 0;
     (void)hipcub::DeviceRadixSort::SortPairsDescending(nullptr, temp, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                                        (const uint32_t*)nullptr, (uint32_t*)nullptr, n);
     return 3 * (size_t)n * sizeof(uint32_t) + temp + 256;
 }
 
-// CPT_SCHEDULE_PREVIOUS: one wave per 8x8 tile; lane k = pixel k of the tile (decode_pixel's
-// layout).  A pixel's draws since the last call are (d - d_prev) / 362437 mod 2^32 (every
+// CPT_SCHEDULE_PREVIOUS: one wave per 8x8 tile; lane k = pixel k of the tile (TileGrid::pixel).
+//  A pixel's draws since the last call are (d - d_prev) / 362437 mod 2^32 (every
 // curand() adds 362437 to d, an odd number: a multiplication by its inverse mod 2^32).
 __global__ void __launch_bounds__(64) k_tile_draws(const uint32_t* __restrict__ d_now, uint32_t* __restrict__ d_prev,
                                                    int width, int n_rows, uint32_t* __restrict__ cost) {
@@ -47,12 +47,11 @@ __global__ void __launch_bounds__(64) k_tile_draws(const uint32_t* __restrict__ 
         return x;
     }();
     static_assert(WEYL * INV == 1u, "inverse of the Weyl step");
-    const int tiles_x = (width + 7) >> 3;
     const uint32_t tile = blockIdx.x;
     const int k = threadIdx.x;
-    const int x = (int)(tile % tiles_x) * 8 + (k & 7), ri = (int)(tile / tiles_x) * 8 + (k >> 3);
+    int x, ri;
     uint32_t draws = 0;
-    if (x < width && ri < n_rows) {
+    if (TileGrid{width, n_rows}.pixel(tile, k, x, ri)) {
         const size_t pix = (size_t)ri * width + x;
         const uint32_t d = d_now[pix];
         draws = (d - d_prev[pix]) * INV;
@@ -91,7 +90,7 @@ static hipError_t sort_tiles_by_cost(const TileScratch& s, int n, uint32_t* orde
 
 hipError_t launch_tile_order_from_draws(const KParams& p, uint32_t* d_prev, void* scratch, size_t scratch_bytes,
                                         uint32_t* order, hipStream_t stream) {
-    const int n = ((p.width + 7) / 8) * ((p.n_rows + 7) / 8);
+    const int n = TileGrid{p.width, p.n_rows}.count();
     if (n <= 0) return hipSuccess;
     const TileScratch s = carve_tile_scratch(scratch, scratch_bytes, n);
     const size_t npix = (size_t)p.n_rows * p.width;
@@ -104,7 +103,7 @@ hipError_t launch_tile_order_from_draws(const KParams& p, uint32_t* d_prev, void
 
 hipError_t launch_tile_schedule(const KParams& p0, int passes, void* scratch, size_t scratch_bytes, uint32_t* order,
                                 int max_workgroups, hipStream_t stream) {
-    const int n = ((p0.width + 7) / 8) * ((p0.n_rows + 7) / 8);
+    const int n = TileGrid{p0.width, p0.n_rows}.count();
     if (n <= 0) return hipSuccess;
     const TileScratch s = carve_tile_scratch(scratch, scratch_bytes, n);
     hipError_t e = hipMemsetAsync(s.cost, 0, (size_t)n * sizeof(uint32_t), stream);

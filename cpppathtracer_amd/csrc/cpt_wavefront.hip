@@ -39,7 +39,7 @@ __device__ __forceinline__ uint32_t wave_append(bool alive, uint32_t* counter) {
     uint32_t base = 0;
     if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(counter, (uint32_t)__popcll(m));
     base = __shfl(base, leader);
-    return base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    return base + lane_rank(m);
 }
 
 __device__ __forceinline__ void load_rng(const KParams& p, size_t npix, size_t pix, Xorwow& s) {
@@ -188,7 +188,7 @@ __global__ void __launch_bounds__(256) k_wf_shade(const KParams p, WfState w, co
             for (int v = 0; v < 4; ++v)
                 if (k < key || (k == key && v < wv)) pos += s_cnt[k][v];
         const uint64_t mine = mk_[key];
-        pos += __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
+        pos += lane_rank(mine);
         s_slot[pos] = i0;
         __syncthreads();
         const uint32_t i = s_slot[threadIdx.x];
@@ -271,7 +271,7 @@ __global__ void __launch_bounds__(256) k_wf_shade(const KParams p, WfState w, co
         __syncthreads();
         uint32_t slot = s_app[4];
         for (int v = 0; v < wv; ++v) slot += s_app[v];
-        slot += __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
+        slot += lane_rank(am);
         if (alive) {
             const int ob = sb ^ 1;
             qout[slot] = pix;
@@ -295,15 +295,13 @@ __global__ void __launch_bounds__(256) k_wf_shade(const KParams p, WfState w, co
 // Tile-ordered identity queue: the frame's pixels walked in 8x8 tiles (a wave's 64 consecutive
 // ids are one tile), so each wave's first-bounce rays are coherent.
 __global__ void k_wf_ident(int width, int n_rows, int32_t* q, uint32_t* count) {
-    const int tiles_x = (width + 7) / 8;
-    const uint32_t n_work = (uint32_t)tiles_x * ((n_rows + 7) / 8) * 64u;
+    const TileGrid grid{width, n_rows};
+    const uint32_t n_work = (uint32_t)grid.count() * 64u;
     for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < n_work; id += gridDim.x * blockDim.x) {
-        const uint32_t tile = id >> 6, k = id & 63;
-        const int x = (int)(tile % tiles_x) * 8 + (int)(k & 7);
-        const int ri = (int)(tile / tiles_x) * 8 + (int)(k >> 3);
+        int x, ri;
         // the valid pixels of a wave's 64 consecutive ids (one tile) get consecutive slots, one
         // counter atomic per wave (the queue's order only steers coherence, not any result)
-        const bool valid = x < width && ri < n_rows;
+        const bool valid = grid.pixel(id >> 6, id & 63, x, ri);
         const uint32_t slot = wave_append(valid, count);
         if (valid) q[slot] = ri * width + x;
     }

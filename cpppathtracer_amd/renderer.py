@@ -15,6 +15,7 @@ from ._lib import (CPT_PATH_WAVEFRONT, CPT_RENDER_ACCUMULATE, CPT_RENDER_AUX, CP
                    CPT_TRAVERSAL_PLAIN_LEAVES, CptError, check)
 
 PATHS = ("megakernel", "wavefront")
+from .tiling import tile_grid
 from .types import CAMERA_DTYPE, OBJECT_DTYPE
 
 
@@ -262,7 +263,7 @@ class Renderer:
         pixel (the maximum over the tile's pixels, not their sum) over `passes` passes from the
         current RNG states (nothing written back), [tiles_y, tiles_x] uint32."""
         c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
-        ty, tx = (self.n_rows + 7) // 8, (self.width + 7) // 8
+        ty, tx = tile_grid(self.width, self.n_rows)
         out = np.zeros((ty, tx), dtype=np.uint32)
         f = CPT_TRAVERSAL_ORDERED if ordered else 0
         f |= CPT_TRAVERSAL_PLAIN_LEAVES if ordered == "plain" else 0
@@ -398,7 +399,7 @@ class Renderer:
         """DIAGNOSTIC: a device-built tile list (cpt_debug_read_tile_order) as uint32 tile ids:
         which = 0 the cost schedule's order, 1 the CPT_SCHEDULE_PREVIOUS order, 2 the list the
         pending adaptive round renders.  Waits for the context's stream."""
-        ty, tx = (self.n_rows + 7) // 8, (self.width + 7) // 8
+        ty, tx = tile_grid(self.width, self.n_rows)
         out = np.zeros(max(1, ty * tx), dtype=np.uint32)
         n = ctypes.c_size_t(0)
         self._check(self._L.cpt_debug_read_tile_order(self._ctx, int(which), _p(out), ty * tx, ctypes.byref(n)))

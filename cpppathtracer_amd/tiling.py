@@ -13,6 +13,12 @@ import numpy as np
 BLOCK_ROWS = 8   # one row of the megakernel's 8x8 pixel tiles
 
 
+def tile_grid(width: int, n_rows: int) -> tuple:
+    """(tiles_y, tiles_x) of the 8x8 tiles over `n_rows` rows of `width` pixels, the tiles at the
+    right and bottom edges partly outside (csrc/cpt_tiles.hpp TileGrid)."""
+    return (n_rows + 7) // 8, (width + 7) // 8
+
+
 def weak_scaled_size(width: int, height: int, world: int) -> tuple:
     """Weak scaling (bench.py --scaling weak): N times the pixels at the same aspect, i.e. each
     axis scaled by sqrt(N) and rounded to whole 8x8 tiles (N = 4: 1920x1080 -> 3840x2160)."""

@@ -7,7 +7,11 @@ model only decides which round each 8x8 tile stops at; the expected accumulator,
 map and first-hit normals take each pixel from its tile's stop round.  numpy's float32 `+ - * /` and
 sqrt are the correctly rounded IEEE operations, one rounding per operation as written.
 """
+import math
+
 import numpy as np
+
+from cpppathtracer_amd.tiling import tile_grid
 
 F = np.float32
 REL_FLOOR = F(1e-3)
@@ -41,7 +45,7 @@ def batch_luma(S, P):
 
 def tile_of_pixel(width, n_rows):
     i = np.arange(n_rows * width)
-    return ((i // width) // 8) * ((width + 7) // 8) + (i % width) // 8
+    return ((i // width) // 8) * tile_grid(width, n_rows)[1] + (i % width) // 8
 
 
 def oracle_rounds(oracle, objs, cam, env, rows, batch, rounds, depth, rng, acc0=None, aux=False):
@@ -67,7 +71,7 @@ def run(snaps, width, n_rows, batch, min_spp, max_spp, t, acc0=None):
     rounds = max_spp // batch
     assert len(snaps) == rounds and min_spp % batch == 0 and max_spp % batch == 0
     tile = tile_of_pixel(width, n_rows)
-    n_tiles = ((width + 7) // 8) * ((n_rows + 7) // 8)
+    n_tiles = math.prod(tile_grid(width, n_rows))
     P = np.zeros((npix, 4), dtype=np.float32) if acc0 is None else np.array(acc0, dtype=np.float32, copy=True)
     m1, m2, k = (np.zeros(npix, dtype=np.float32) for _ in range(3))
     rel = np.full(npix, np.inf, dtype=np.float32)

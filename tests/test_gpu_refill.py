@@ -18,6 +18,7 @@ quarter of that),
     1 workgroup, the frames of 2048 .. 4095 ids at 2): more pixels than lanes, which is what
     forces some lane to take a second pixel (pigeonhole).
 """
+import math
 from contextlib import contextmanager
 
 import numpy as np
@@ -29,6 +30,7 @@ import test_gpu_parity as tp
 from test_gpu_parity import _check_stats, _kw, _run_both
 
 from cpppathtracer_amd import CptError, camera_get_copy, scenes
+from cpppathtracer_amd.tiling import tile_grid
 
 pytestmark = pytest.mark.gpu
 
@@ -44,7 +46,7 @@ def capped(gpu, W, n_rows, max_workgroups, lanes_per_wave=64, strict=True):
     `gpu` fixture is session-wide), and the precondition that a render of a W x n_rows frame under
     it cannot finish without a lane taking a second pixel."""
     lanes = max_workgroups * 16 * lanes_per_wave
-    ids = ((W + 7) // 8) * ((n_rows + 7) // 8) * 64
+    ids = math.prod(tile_grid(W, n_rows)) * 64
     assert W * n_rows > lanes, (W, n_rows, lanes)
     if strict:
         assert ids >= 2 * lanes, (ids, lanes)
@@ -80,7 +82,7 @@ def test_hook_arguments(gpu):
 def _wgs(W, H):
     """(max_workgroups, strict) a W x H frame runs at: 1 and 2; 2 only with more pixels than 2048
     lanes; strict where it has two ids per lane."""
-    ids = ((W + 7) // 8) * ((H + 7) // 8) * 64
+    ids = math.prod(tile_grid(W, H)) * 64
     return [(wg, ids >= 2048 * wg) for wg in (1, 2) if W * H > 1024 * wg]
 
 
@@ -169,7 +171,7 @@ def test_long_chains_capped(gpu, oracle_mod, sky, wg, strict, path):
     "+cons" keepers that take hand-overs and fresh pixels in one render.  The schedules: "tiles"
     and "cost", each with and without consolidation."""
     W, H = LONG["W"], LONG["H"]
-    assert ((W + 7) // 8) * ((H + 7) // 8) * 64 == 2880 > 1024 * wg
+    assert math.prod(tile_grid(W, H)) * 64 == 2880 > 1024 * wg
     kw = _kw(path)
     assert kw["ordered"] is True and kw.get("schedule", "tiles") == ("cost" if "timed" in path else "tiles")
     assert bool(kw.get("consolidate")) == ("cons" in path)
@@ -279,7 +281,7 @@ def _pilot_costs(gpu, cam, W, H, passes, depth, ordered):
     for wg, lpw in GRIDS:
         lanes = wg * 16 * lpw
         # (1, 4) refills on every frame; the full-width grids where the frame has the pixels
-        strict = ((W + 7) // 8) * ((H + 7) // 8) * 64 >= 2 * lanes and W * H > lanes
+        strict = math.prod(tile_grid(W, H)) * 64 >= 2 * lanes and W * H > lanes
         assert strict or lpw == 64
         refilled += strict
         gpu.set_debug_grid(wg, lpw)
@@ -301,7 +303,7 @@ def test_pilot_costs_do_not_depend_on_the_grid(gpu, sky, frame, passes, ordered)
     (its heaviest pixel's work) is the same however many pixels the lane ran before."""
     cam, W, H = _pilot_setup(gpu, sky, frame)
     if frame == "s1000_200":
-        assert ((W + 7) // 8) * ((H + 7) // 8) * 64 >= 2 * 1024   # refills at (1, 64) too
+        assert math.prod(tile_grid(W, H)) * 64 >= 2 * 1024   # refills at (1, 64) too
     out = _pilot_costs(gpu, cam, W, H, passes, 8, ordered)
     assert (out[None] > 0).all()
     for grid in GRIDS:

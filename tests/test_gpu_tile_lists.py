@@ -28,6 +28,7 @@ pilot's costs, the previous-pass order that of each tile's RNG draws; nothing el
 reads an order back (the render-parity tests only prove a permutation).
 """
 import ctypes
+import math
 
 import adaptive_model as am
 import numpy as np
@@ -36,6 +37,7 @@ from test_gpu_adaptive import _assert_state
 
 from cpppathtracer_amd import CptError, Renderer, _lib, camera_get_copy, scenes, types
 from cpppathtracer_amd._lib import CPT_SCHEDULE_COST, CPT_TRAVERSAL_ORDERED
+from cpppathtracer_amd.tiling import tile_grid
 
 pytestmark = pytest.mark.gpu
 
@@ -55,7 +57,7 @@ def _frame(gpu, sky, objs, W, H, seed=SEED):
 
 
 def _n_tiles(W, H):
-    return ((W + 7) // 8) * ((H + 7) // 8)
+    return math.prod(tile_grid(W, H))
 
 
 def _stable_descending(keys):
@@ -239,7 +241,7 @@ def _assert_stable_descending(order, cost):
     np.testing.assert_array_equal(order, _stable_descending(cost))
 
 
-PILOT_MAX, PILOT_DIV = 16, 128   # cpt_capi.cpp cost_pilot_passes
+PILOT_MAX, PILOT_DIV = 16, 128   # cpt_capi_render.cpp cost_pilot_passes
 
 
 @pytest.mark.parametrize("W,H", [(8, 8), (20, 12), (132, 68), (268, 252)])
@@ -308,7 +310,7 @@ def test_previous_order_is_the_stable_sort_of_the_draws(gpu, sky, W, H):
     rebuilds it (before this test existed the old order stayed valid across a re-seed)."""
     assert (WEYL * WEYL_INV) % (1 << 32) == 1
     objs = scenes.scene_s1000(n=40)
-    tx, ty = (W + 7) // 8, (H + 7) // 8
+    ty, tx = tile_grid(W, H)
     cam = _frame(gpu, sky, objs, W, H)
     assert _status(gpu, 1) == STATE   # no such render yet
     for seed in (SEED, 77):
