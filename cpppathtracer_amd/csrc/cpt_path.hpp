@@ -437,6 +437,7 @@ __device__ __forceinline__ bool slab_reject_octant(const Node& nd, const RayK& r
 // instead of 64-bit address arithmetic, and out-of-range offsets read 0 instead of needing a
 // clamp (the walk never uses a node past its order's end).
 typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
+typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
 
 struct BufSrc {
     __amdgpu_buffer_rsrc_t rsrc;
@@ -668,26 +669,24 @@ typedef __attribute__((address_space(3))) int16_t lds_i16;
 
 struct WideNode {
     f2v e[3][2], x[3][2];   // entry / exit planes per axis, children (0,1) and (2,3)
-    int ref[4];
     uint32_t r01, r23;      // the refs as stored: slots 0 | 1 << 16, 2 | 3 << 16
 };
 
 // A node of the compact image for a ray whose direction signs are (sx, sy, sz): the entry
 // planes of an axis are the slots' max planes when the ray runs toward -axis, else the min
-// planes, i.e. the planes the ray enters through; quad(k) reads the node's k-th 16 B.
-template <typename QUAD>
-__device__ __forceinline__ WideNode wide_node(const QUAD& quad, int sx, int sy, int sz) {
+// planes, i.e. the planes the ray enters through; quad(k) reads the node's k-th 16 B, refs()
+// the 8 B of child refs that open its last quad.
+template <typename QUAD, typename REFS>
+__device__ __forceinline__ WideNode wide_node(const QUAD& quad, const REFS& refs, int sx, int sy, int sz) {
     WideNode n;
     const uint4 ex = quad(sx), xx = quad(1 - sx), ey = quad(2 + sy), xy = quad(3 - sy), ez = quad(4 + sz),
                 xz = quad(5 - sz);
-    const uint4 r = quad(6);
+    const uint2 r = refs();
     auto lo = [](uint4 v) { return f2v{__uint_as_float(v.x), __uint_as_float(v.y)}; };
     auto hi = [](uint4 v) { return f2v{__uint_as_float(v.z), __uint_as_float(v.w)}; };
     n.e[0][0] = lo(ex); n.e[0][1] = hi(ex); n.x[0][0] = lo(xx); n.x[0][1] = hi(xx);
     n.e[1][0] = lo(ey); n.e[1][1] = hi(ey); n.x[1][0] = lo(xy); n.x[1][1] = hi(xy);
     n.e[2][0] = lo(ez); n.e[2][1] = hi(ez); n.x[2][0] = lo(xz); n.x[2][1] = hi(xz);
-    n.ref[0] = (int)(int16_t)(r.x & 0xffffu); n.ref[1] = (int)(int16_t)(r.x >> 16);
-    n.ref[2] = (int)(int16_t)(r.y & 0xffffu); n.ref[3] = (int)(int16_t)(r.y >> 16);
     n.r01 = r.x;
     n.r23 = r.y;
     return n;
@@ -706,10 +705,13 @@ __device__ __forceinline__ WideNode load_wide_node(const uint4* tree, int n_lds,
         typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
         typedef __attribute__((address_space(3))) const v4u_t lds_v4u;
         typedef __attribute__((address_space(3))) const uint4 lds_u4;
+        typedef unsigned int v2u_t __attribute__((ext_vector_type(2)));
+        typedef __attribute__((address_space(3))) const v2u_t lds_v2u;
         uint32_t a;
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(a) : "v"(cur), "s"(112u), "v"((uint32_t)(uintptr_t)(lds_u4*)tree));
         lds_v4u* const q = (lds_v4u*)(uintptr_t)a;
-        return wide_node([&](int k) { const v4u_t v = q[k]; return make_uint4(v.x, v.y, v.z, v.w); }, sx, sy, sz);
+        return wide_node([&](int k) { const v4u_t v = q[k]; return make_uint4(v.x, v.y, v.z, v.w); },
+                         [&]() { const v2u_t v = *(lds_v2u*)(q + 6); return make_uint2(v.x, v.y); }, sx, sy, sz);
     }
     const uint32_t off = image_off + (uint32_t)cur * 112u;
     return wide_node(
@@ -717,13 +719,17 @@ __device__ __forceinline__ WideNode load_wide_node(const uint4* tree, int n_lds,
             const v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 16u * (uint32_t)k, 0, 0);
             return make_uint4(v.x, v.y, v.z, v.w);
         },
+        [&]() {
+            const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off + 96u, 0, 0);
+            return make_uint2(v.x, v.y);
+        },
         sx, sy, sz);
 }
 
-// Hit mask of children (a, b) of a pair: slab_reject_octant for each; lo_a / lo_b get their
-// sort keys (slab_pass's lo').
-__device__ __forceinline__ uint32_t wide_pair(const f2v e[3], const f2v x[3], const RayK& ray, float limit,
-                                              float& lo_a, float& lo_b) {
+// Children (a, b) of a pair: slab_reject_octant for each (pa / pb: the child is hit); lo_a /
+// lo_b get their sort keys (slab_pass's lo').
+__device__ __forceinline__ void wide_pair(const f2v e[3], const f2v x[3], const RayK& ray, float limit,
+                                          float& lo_a, float& lo_b, bool& pa, bool& pb) {
     lo_a = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(e[0].x, ray.inx, ray.nx), __builtin_fmaf(e[1].x, ray.iny, ray.ny)),
                            __builtin_fmaf(e[2].x, ray.inz, ray.nz));
     lo_b = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaf(e[0].y, ray.inx, ray.nx), __builtin_fmaf(e[1].y, ray.iny, ray.ny)),
@@ -732,8 +738,8 @@ __device__ __forceinline__ uint32_t wide_pair(const f2v e[3], const f2v x[3], co
                                        __builtin_fmaf(x[2].x, ray.ifz, ray.fz));
     const float hi_b = __builtin_fminf(__builtin_fminf(__builtin_fmaf(x[0].y, ray.ifx, ray.fx), __builtin_fmaf(x[1].y, ray.ify, ray.fy)),
                                        __builtin_fmaf(x[2].y, ray.ifz, ray.fz));
-    const bool pa = slab_pass(lo_a, hi_a, ray.t3, limit), pb = slab_pass(lo_b, hi_b, ray.t3, limit);
-    return (pa ? 1u : 0u) | (pb ? 2u : 0u);
+    pa = slab_pass(lo_a, hi_a, ray.t3, limit);
+    pb = slab_pass(lo_b, hi_b, ray.t3, limit);
 }
 
 // Child refs (the image's int16 words, cpt_host_bvh.cpp linearise_wide): >= 0 a wide node, -1 none,
@@ -839,32 +845,60 @@ __device__ __forceinline__ int trace_wide(const KParams& p, __amdgpu_buffer_rsrc
                 const f2v e01[3] = {n.e[0][0], n.e[1][0], n.e[2][0]}, x01[3] = {n.x[0][0], n.x[1][0], n.x[2][0]};
                 const f2v e23[3] = {n.e[0][1], n.e[1][1], n.e[2][1]}, x23[3] = {n.x[0][1], n.x[1][1], n.x[2][1]};
                 float lo[4];
-                const uint32_t m = wide_pair(e01, x01, ray, limit, lo[0], lo[1]) |
-                                   (wide_pair(e23, x23, ray, limit, lo[2], lo[3]) << 2);
+                bool hit[4];
+                wide_pair(e01, x01, ray, limit, lo[0], lo[1], hit[0], hit[1]);
+                wide_pair(e23, x23, ray, limit, lo[2], lo[3], hit[2], hit[3]);
                 // The hit child walked next is the one with the nearest entry distance (first
                 // slot on ties): the minimum of sort keys made of the distance's bits with the
                 // slot in the two low bits (integer order is the float order for the distances
                 // >= 0; the few negative ones, of boxes the ray starts in, come first, and ties
                 // within 4 ulps go to the first slot -- the order only steers the walk, the hits
-                // do not depend on it).  The other hits are pushed (slot 3 first) without
-                // branches: every slot is written at the top, and the top moves past it only
-                // when it is pushed (the host bounds the depth, so a write at an unmoved top
-                // stays inside the lane's stack).
-                int key = 0x7fffffff;
+                // do not depend on it).  A child that is not hit has the key INT_MAX, which no hit
+                // child has (a distance that passes the slab test is no NaN), so each key comes
+                // from the slab compare's own lane mask and the hit mask is never made an integer.
+                // The other hits are pushed (slot 3 first) without branches: every slot is
+                // written at the top, and the top moves past it only when it is pushed (the host
+                // bounds the depth, so a write at an unmoved top stays inside the lane's stack).
+                constexpr int NO_HIT = 0x7fffffff;
+                int kk[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int kk = (__float_as_int(lo[k]) & ~3) | k;
-                    key = ((m >> k) & 1u) && kk < key ? kk : key;
-                }
-                const int bk = key & 3;
-                const uint32_t pm = m & ~(1u << bk);   // the hits pushed
+                for (int k = 0; k < 4; ++k) kk[k] = hit[k] ? (__float_as_int(lo[k]) & ~3) | k : NO_HIT;
+                const int k01 = kk[0] < kk[1] ? kk[0] : kk[1], k23 = kk[2] < kk[3] ? kk[2] : kk[3];
+                const int key = k01 < k23 ? k01 : k23;
 #pragma unroll
                 for (int k = 3; k >= 0; --k) {
-                    *top = (int16_t)n.ref[k];
-                    top += __builtin_amdgcn_ubfe(pm, (uint32_t)k, 1u) * BLK;
+                    // the ref's own 16 bits, from the word as stored (a d16 / d16-hi store)
+                    const uint32_t w2 = k & 2 ? n.r23 : n.r01;
+                    *top = (int16_t)(k & 1 ? w2 >> 16 : w2);
+                    // pushed: hit and not the nearest.  The two compares' lane masks are combined
+                    // as masks (one scalar and); the result selects 0 or 64, which one
+                    // v_lshl_add scales to the entry's BLK * 2 bytes and adds to the top.  As a
+                    // C++ bool the condition costs a second v_cndmask per slot, and as C++
+                    // arithmetic the compiler sums the four selects first and scales each prefix
+                    // sum (three more adds), hence the inline assembly.  It assumes wave64: the
+                    // select's mask operand is the 64-bit ballot.
+                    const uint64_t pushed =
+                        __builtin_amdgcn_ballot_w64(hit[k]) & __builtin_amdgcn_ballot_w64(kk[k] != key);
+                    uint32_t adv;
+                    // (64 is an inline constant; the entry's BLK * 2 bytes as a literal would
+                    // hold a VGPR across the loop)
+                    static_assert(BLK >= 32 && (BLK & (BLK - 1)) == 0, "an entry is 64 bytes times a power of two");
+                    asm("v_cndmask_b32 %0, 0, 64, %1" : "=v"(adv) : "s"(pushed));
+                    uint32_t next;
+                    asm("v_lshl_add_u32 %0, %1, %2, %3"
+                        : "=v"(next)
+                        : "v"(adv), "n"(__builtin_ctz(BLK / 32)), "v"((uint32_t)(uintptr_t)top));
+                    top = (lds_i16*)(uintptr_t)next;
                 }
-                const uint32_t word = (bk & 2) ? n.r23 : n.r01;
-                cur = m == 0 ? pop() : (int)(int16_t)(word >> ((bk & 1) << 4));
+                // the nearest child's ref, sign-extended: bit 1 of the key's slot picks the word,
+                // bit 0 the half (v_bfe_i32 reads the low five bits of its offset: 0 or 16)
+                const uint32_t word = (key & 2) ? n.r23 : n.r01;
+                // No child is hit iff slot 3 is not hit and its key (then INT_MAX) is the minimum:
+                // the two masks the push of slot 3 already has.  (`key == NO_HIT` holds the
+                // literal in an SGPR across the whole kernel, which cost up to 8 more spilled
+                // SGPRs in the HYB and consolidating instantiations.)
+                const bool none = !(hit[3] || kk[3] != key);
+                cur = none ? pop() : __builtin_amdgcn_sbfe((int)word, (uint32_t)key << 4, 16u);
                 if (cur <= -2 && parked < 0) {   // park the nearest leaf at once
                     parked = leaf_of(cur);
                     cur = pop();
