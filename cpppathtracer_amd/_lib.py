@@ -91,6 +91,11 @@ PROTOTYPES = {
     "cpt_last_filter_ms": (_I, [_P, _P]),
     "cpt_filter_prepare_host": (_I, [_SZ, _P, _P, _P, _P]),
     "cpt_filter_level_host": (_I, [_I, _I, _I, _P, _P, _P, ctypes.c_float, _I, _P]),
+    "cpt_gbuffer": (_I, [_P, _P, _U32]),
+    "cpt_read_gbuffer": (_I, [_P, _P, _P, _P, _P, _SZ]),
+    "cpt_trace_rays": (_I, [_P, _SZ, _P, _P, _P, _U32, _P, _P, _P]),
+    "cpt_pick": (_I, [_P, _P, _I, _I, _U32, _P, _P]),
+    "cpt_last_query_ms": (_I, [_P, _P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1
@@ -105,6 +110,7 @@ CPT_SCHEDULE_COST = 0x800
 CPT_SCHEDULE_CONSOLIDATE = 0x1000
 CPT_SCHEDULE_NO_CONSOLIDATE = 0x2000
 CPT_SCHEDULE_PREVIOUS = 0x4000
+CPT_ERR_INVALID_ARG = 1
 CPT_ERR_STATE = 5
 CPT_ERR_DEVICE = 7   # a kernel abandoned work (reported at the next synchronising call)
 

@@ -21,6 +21,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_selftest.hip"),
     os.path.join(CSRC, "cpt_kernels.hip"),
     os.path.join(CSRC, "cpt_wavefront.hip"),
+    os.path.join(CSRC, "cpt_query.hip"),
     os.path.join(CSRC, "cpt_capi.cpp"),
     os.path.join(CSRC, "cpt_capi_render.cpp"),
     os.path.join(CSRC, "cpt_capi_gather.cpp"),
@@ -28,6 +29,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_capi_probes.cpp"),
     os.path.join(CSRC, "cpt_capi_adaptive.cpp"),
     os.path.join(CSRC, "cpt_capi_filter.cpp"),
+    os.path.join(CSRC, "cpt_capi_query.cpp"),
     os.path.join(CSRC, "cpt_scene.cpp"),
     os.path.join(CSRC, "cpt_host_bvh.cpp"),
     os.path.join(CSRC, "cpt_host_rng.cpp"),

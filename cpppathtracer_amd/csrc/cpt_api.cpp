@@ -759,6 +759,80 @@ bool PathTracer::SaveFilteredPFM(const std::string& path) {
     return false;
 }
 
+// The current camera with its basis computed, as GetCopy() gives it, but from a copy: the
+// camera's own sample index (the display path's Mix weight) does not move for a query.
+static MotionalCamera query_camera(const MotionalCamera& cam) {
+    MotionalCamera c = cam;
+    cpt_camera_get_copy(reinterpret_cast<cpt_camera*>(&c));
+    return c;
+}
+
+int PathTracer::Pick(int x, int y, float* t) {
+    if (!camera_) {
+        err_ = "Pick: SetCamera first";
+        return -1;
+    }
+    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
+    const MotionalCamera cma = query_camera(*camera_);
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!SyncScene() || !EnsureFrame(cma)) return -1;
+    int32_t object = -1;
+    if (cpt_pick(tiles_[0].ctx, reinterpret_cast<const cpt_camera*>(&cma), x, y, ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u,
+                 &object, t) != CPT_OK) {
+        Fail("cpt_pick", tiles_[0].ctx);
+        return -1;
+    }
+    return object;
+}
+
+// Every tile's G-buffer is queued first, then each is read into its rows of the frame.
+bool PathTracer::ReadGBuffer(std::vector<int32_t>& id, std::vector<float>& t, std::vector<float>& normal3,
+                             std::vector<float>& albedo3) {
+    if (!camera_) {
+        err_ = "ReadGBuffer: SetCamera first";
+        return false;
+    }
+    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
+    const MotionalCamera cma = query_camera(*camera_);
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!SyncScene() || !EnsureFrame(cma)) return false;
+    const uint32_t flags = ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u;
+    for (Tile& tile : tiles_)
+        if (cpt_gbuffer(tile.ctx, reinterpret_cast<const cpt_camera*>(&cma), flags) != CPT_OK)
+            return Fail("cpt_gbuffer", tile.ctx);
+    const size_t w = (size_t)width_, npix = w * height_;
+    id.resize(npix);
+    t.resize(npix);
+    normal3.resize(3 * npix);
+    albedo3.resize(3 * npix);
+    const int n = (int)tiles_.size();
+    if (n == 1) {
+        if (cpt_read_gbuffer(tiles_[0].ctx, id.data(), t.data(), normal3.data(), albedo3.data(), npix) != CPT_OK)
+            return Fail("cpt_read_gbuffer", tiles_[0].ctx);
+        return true;
+    }
+    std::vector<int32_t> tid;
+    std::vector<float> tt, tn, ta;
+    for (int r = 0; r < n; ++r) {
+        const std::vector<int32_t> rows = tile_rows(height_, n, r);
+        const size_t m = rows.size() * w;
+        tid.resize(m);
+        tt.resize(m);
+        tn.resize(3 * m);
+        ta.resize(3 * m);
+        if (cpt_read_gbuffer(tiles_[r].ctx, tid.data(), tt.data(), tn.data(), ta.data(), m) != CPT_OK)
+            return Fail("cpt_read_gbuffer", tiles_[r].ctx);
+        for (size_t k = 0; k < rows.size(); ++k) {
+            const size_t dst = (size_t)rows[k] * w, src = k * w;
+            std::copy(tid.begin() + src, tid.begin() + src + w, id.begin() + dst);
+            std::copy(tt.begin() + src, tt.begin() + src + w, t.begin() + dst);
+            std::copy(tn.begin() + 3 * src, tn.begin() + 3 * (src + w), normal3.begin() + 3 * dst);
+            std::copy(ta.begin() + 3 * src, ta.begin() + 3 * (src + w), albedo3.begin() + 3 * dst);
+        }
+    }
+    return true;
+}
+
 // Counters summed over the tiles (the render flags do not ask for CPT_RENDER_STATS, so these
 // are the counters of the last counting render; GetStats after cpt-level counting renders).
 bool PathTracer::GetStats(cpt_stats* out) {

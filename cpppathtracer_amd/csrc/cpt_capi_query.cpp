@@ -1,0 +1,158 @@
+// cpt_capi_query.cpp — the C-ABI's first-hit queries (include/cpt.h): cpt_gbuffer
+// and its read-out, cpt_trace_rays, cpt_pick and their timing.  The kernel is cpt_query.hip's; it
+// reads the scene and the camera and writes only the buffers named here.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "cpt_context.hpp"
+#include "cpt_query.hpp"
+
+using namespace cpt::ctx;
+
+namespace {
+
+constexpr uint32_t WALK_FLAGS = CPT_TRAVERSAL_ORDERED | CPT_TRAVERSAL_PLAIN_LEAVES;
+constexpr size_t MAX_RAYS = (size_t)1 << 30;   // the kernel's 32-bit lane index, with room
+
+// The kernel parameters of a query: the scene, the walk of `flags`, the frame's rows, and `cam`
+// (nullptr: none, for explicit rays).
+void query_params(cpt_ctx* c, const cpt_camera* cam, uint32_t flags, cpt::KParams& p) {
+    cpt_camera none;
+    std::memset(&none, 0, sizeof(none));
+    none.width = none.height = 1;
+    fill_params(c, cam ? cam : &none, 0, 0, flags, p);
+}
+
+// What cpt_gbuffer and cpt_pick ask before they launch: walk flags only, a scene, a frame, a
+// camera of the frame's size.
+int pixel_query_ok(cpt_ctx* c, const cpt_camera* cam, uint32_t flags, const char* who) {
+    if (flags & ~WALK_FLAGS) return fail(c, CPT_ERR_INVALID_ARG, "%s: flags 0x%x (only CPT_TRAVERSAL_* bits)", who, flags);
+    if (!c->scene_set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_scene first", who);
+    if (!c->frame.set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_frame first", who);
+    if (cam->width != c->width || cam->height != c->height)
+        return fail(c, CPT_ERR_INVALID_ARG, "%s: camera %dx%d vs frame %dx%d", who, cam->width, cam->height, c->width, c->height);
+    return CPT_OK;
+}
+
+// One launch of the query kernel between the timing events.
+int timed_query(cpt_ctx* c, const cpt::KParams& p, const cpt::QueryRays* rays, cpt::QueryPixels px, const cpt::QueryOut& out) {
+    hipStream_t s = c->stream();
+    HIP_TRY(c, hipEventRecord(c->t_query.t0, s));
+    HIP_TRY(c, cpt::launch_ray_query(p, c->d_rank_obj, rays, px, out, s));
+    HIP_TRY(c, hipEventRecord(c->t_query.t1, s));
+    c->t_query.recorded = true;
+    return CPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cpt_gbuffer(cpt_ctx* c, const cpt_camera* cam, uint32_t flags) {
+    if (!c || !cam) return c ? fail(c, CPT_ERR_INVALID_ARG, "cpt_gbuffer: camera is NULL") : CPT_ERR_INVALID_ARG;
+    if (int rc = pixel_query_ok(c, cam, flags, "cpt_gbuffer")) return rc;
+    CPT_REFUSE_PENDING(c, "cpt_gbuffer");
+    if (cpt::ctx::n_tiles(c) > (size_t)(UINT32_MAX / 64))
+        return fail(c, CPT_ERR_UNSUPPORTED, "cpt_gbuffer: frame of %zu 8x8 tiles (max %u)", cpt::ctx::n_tiles(c), UINT32_MAX / 64);
+    HIP_TRY(c, hipSetDevice(c->device));
+    GBufferState& g = c->frame.gbuffer;
+    const size_t npix = c->npix();
+    int rc;
+    if ((rc = g.d_id.ensure(c, npix)) != CPT_OK || (rc = g.d_t.ensure(c, npix)) != CPT_OK ||
+        (rc = g.d_normal.ensure(c, 3 * npix)) != CPT_OK || (rc = g.d_albedo.ensure(c, 3 * npix)) != CPT_OK)
+        return rc;
+    cpt::KParams p;
+    query_params(c, cam, flags, p);
+    const cpt::QueryOut out{g.d_id, g.d_t, g.d_normal, g.d_albedo};
+    if ((rc = timed_query(c, p, nullptr, cpt::QueryPixels{-1, -1}, out)) != CPT_OK) return rc;
+    g.valid = true;
+    return CPT_OK;
+}
+
+int cpt_read_gbuffer(cpt_ctx* c, int32_t* id, float* t, float* normal3, float* albedo3, size_t capacity_pixels) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    const GBufferState& g = c->frame.gbuffer;
+    if (!c->frame.set || !g.valid) return fail(c, CPT_ERR_STATE, "cpt_read_gbuffer: cpt_gbuffer first");
+    const size_t n = c->npix();
+    if (capacity_pixels < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_gbuffer: %zu < %zu pixels", capacity_pixels, n);
+    if (int rc = sync_checked(c)) return rc;
+    if (n == 0) return CPT_OK;
+    if (id) HIP_TRY(c, hipMemcpy(id, g.d_id, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (t) HIP_TRY(c, hipMemcpy(t, g.d_t, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (normal3) HIP_TRY(c, hipMemcpy(normal3, g.d_normal, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (albedo3) HIP_TRY(c, hipMemcpy(albedo3, g.d_albedo, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return CPT_OK;
+}
+
+int cpt_trace_rays(cpt_ctx* c, size_t n, const float* origin3, const float* dir3, const float* tmin, uint32_t flags,
+                   int32_t* id, float* t, float* normal3) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    if (flags & ~WALK_FLAGS) return fail(c, CPT_ERR_INVALID_ARG, "cpt_trace_rays: flags 0x%x (only CPT_TRAVERSAL_* bits)", flags);
+    if (n > MAX_RAYS) return fail(c, CPT_ERR_INVALID_ARG, "cpt_trace_rays: %zu rays (max %zu)", n, MAX_RAYS);
+    if (n > 0 && (!origin3 || !dir3 || !id || !t || !normal3))
+        return fail(c, CPT_ERR_INVALID_ARG, "cpt_trace_rays: origin3, dir3, id, t and normal3 must not be NULL");
+    if (!c->scene_set) return fail(c, CPT_ERR_STATE, "cpt_trace_rays: cpt_set_scene first");
+    if (n == 0) return CPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // all device memory before the first copy: nothing is allocated between the launch and the read-back
+    int rc;
+    if ((rc = c->d_query_rays.ensure(c, 7 * n)) != CPT_OK || (rc = c->d_query_out.ensure(c, 4 * n)) != CPT_OK ||
+        (rc = c->d_query_id.ensure(c, n)) != CPT_OK)
+        return rc;
+    hipStream_t s = c->stream();
+    float* const d_o = c->d_query_rays;
+    float* const d_d = d_o + 3 * n;
+    float* const d_tmin = d_d + 3 * n;
+    float* const d_t = c->d_query_out;
+    float* const d_n = d_t + n;
+    HIP_TRY(c, hipMemcpyAsync(d_o, origin3, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(d_d, dir3, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
+    if (tmin) HIP_TRY(c, hipMemcpyAsync(d_tmin, tmin, n * sizeof(float), hipMemcpyHostToDevice, s));
+    cpt::KParams p;
+    query_params(c, nullptr, flags, p);
+    const cpt::QueryRays rays{d_o, d_d, tmin ? d_tmin : nullptr, (uint32_t)n};
+    const cpt::QueryOut out{c->d_query_id, d_t, d_n, nullptr};
+    if ((rc = timed_query(c, p, &rays, cpt::QueryPixels{-1, -1}, out)) != CPT_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(id, c->d_query_id, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(t, d_t, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(normal3, d_n, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s));
+    return sync_checked(c);
+}
+
+int cpt_pick(cpt_ctx* c, const cpt_camera* cam, int x, int y, uint32_t flags, int32_t* object, float* t) {
+    if (!c || !cam || !object)
+        return c ? fail(c, CPT_ERR_INVALID_ARG, "cpt_pick: camera and object must not be NULL") : CPT_ERR_INVALID_ARG;
+    if (int rc = pixel_query_ok(c, cam, flags, "cpt_pick")) return rc;
+    if (x < 0 || x >= c->width || y < 0 || y >= c->height)
+        return fail(c, CPT_ERR_INVALID_ARG, "cpt_pick: pixel (%d, %d) outside the %dx%d frame", x, y, c->width, c->height);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->d_query_out.ensure(c, 4)) != CPT_OK || (rc = c->d_query_id.ensure(c, 1)) != CPT_OK) return rc;
+    cpt::KParams p;
+    query_params(c, cam, flags, p);
+    float* const d_t = c->d_query_out;
+    const cpt::QueryOut out{c->d_query_id, d_t, d_t + 1, nullptr};
+    if ((rc = timed_query(c, p, nullptr, cpt::QueryPixels{x, y}, out)) != CPT_OK) return rc;
+    hipStream_t s = c->stream();
+    int32_t h_id = -1;
+    float h_t = 0.f;
+    HIP_TRY(c, hipMemcpyAsync(&h_id, c->d_query_id, sizeof(h_id), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(&h_t, d_t, sizeof(h_t), hipMemcpyDeviceToHost, s));
+    if ((rc = sync_checked(c)) != CPT_OK) return rc;
+    *object = h_id;
+    if (t) *t = h_t;
+    return CPT_OK;
+}
+
+int cpt_last_query_ms(cpt_ctx* c, float* ms) {
+    if (!c || !ms) return CPT_ERR_INVALID_ARG;
+    if (!c->t_query.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_query_ms: no query yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->t_query.t1));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->t_query.t0, c->t_query.t1));
+    return CPT_OK;
+}
+
+}  // extern "C"

@@ -2,7 +2,8 @@
 // implementation files share: cpt_capi.cpp (context, frame, RNG, accumulator, counters),
 // cpt_capi_render.cpp (render launches, tile schedules, timing), cpt_capi_adaptive.cpp (adaptive
 // render), cpt_capi_filter.cpp (a-trous filter), cpt_capi_gather.cpp (row-tile gather),
-// cpt_capi_display.cpp (display path), cpt_capi_probes.cpp (diagnostic probes, self-tests) and
+// cpt_capi_display.cpp (display path), cpt_capi_query.cpp (G-buffer, ray queries, picking),
+// cpt_capi_probes.cpp (diagnostic probes, self-tests) and
 // cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  Host code only.
 #pragma once
 
@@ -126,6 +127,14 @@ struct FilterState {
     int result = -1;             // the plane that holds the last call's result (-1: no call yet)
 };
 
+// The G-buffer (cpt_capi_query.cpp; allocated on the frame's first cpt_gbuffer).
+struct GBufferState {
+    DevBuf<int32_t> d_id;               // object index per pixel (-1: miss)
+    DevBuf<float> d_t;                  // hit distance
+    DevBuf<float> d_normal, d_albedo;   // [npix][3] each
+    bool valid = false;                 // a cpt_gbuffer has been queued since cpt_set_frame
+};
+
 struct Frame {
     bool set = false, rng_set = false;
     DevBuf<int32_t> d_rows;
@@ -139,6 +148,7 @@ struct Frame {
     DisplayBand display;
     AdaptiveState adaptive;
     FilterState filter;
+    GBufferState gbuffer;
 };
 
 // A pair of timing events around a subsystem's last launches, once they have been recorded.
@@ -160,6 +170,7 @@ struct cpt_ctx {
     DevEvent ev_main;      // after the cost schedule's pilot: the dominant kernel(s) only, to t_render.t1
     TimedSpan t_display;   // the last display kernel (k_denoise_rows)
     TimedSpan t_filter;    // the last cpt_filter_frame's launches
+    TimedSpan t_query;     // the last query kernel (cpt_gbuffer, cpt_trace_rays, cpt_pick)
     std::string err;
 
     // scene
@@ -178,6 +189,10 @@ struct cpt_ctx {
     std::vector<int> mat_of_obj;       // object index -> material index
     DevBuf<Node> d_nodes;
     DevBuf<Mat> d_mats;
+    // reference-order position -> object index (-1: an internal node): what a leaf's rank
+    // (Node::miss) names, for the ray queries.  Fixed with the topology: a refit leaves it alone.
+    std::vector<int32_t> rank_obj;
+    DevBuf<int32_t> d_rank_obj;
     bool scene_set = false;
     // device refit (cpt_update_objects): the plan of both trees (ids: reference tree, then walk
     // tree), parents, heights, each object's walk-tree leaf, the boxes as built
@@ -227,6 +242,10 @@ struct cpt_ctx {
     std::vector<GatherMap> gather_maps;
     DevBuf<float4> d_gather;
     DevBuf<float> d_gather_stat;   // a staged source's moment planes (planar [4][src npix])
+    // ray queries (cpt_trace_rays, cpt_pick): the rays ([n][3] origins, [n][3] directions, [n]
+    // tmin) and their results ([n] t, [n][3] normals; ids apart), sized before the launch
+    DevBuf<float> d_query_rays, d_query_out;
+    DevBuf<int32_t> d_query_id;
     // adaptive rounds (cpt_adaptive_begin / _step): the read-back of a round, {tiles kept, pixels
     // rendered, device error word}, and the event recorded behind it
     cpt::ctx::HostPinned<uint32_t> h_ad_words;

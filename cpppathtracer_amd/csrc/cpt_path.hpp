@@ -596,10 +596,24 @@ __device__ __forceinline__ bool ranked_leaf_test(const Node& nd, const RayK& ray
     return true;
 }
 
+// What a walk hands back about its winner (the walks' WIN parameter): the leaf's `code` alone, as
+// an int (the integrator's kernels), or with it the leaf's reference-order rank (Node::miss) and
+// the hit distance (the ray queries, cpt_query.hip).
+struct Winner {
+    int code, rank;
+    float t;
+};
+__device__ __forceinline__ void put_winner(int& out, const Node& w, float) { out = w.code; }
+__device__ __forceinline__ void put_winner(Winner& out, const Node& w, float t) {
+    out.code = w.code;
+    out.rank = w.miss;
+    out.t = t;
+}
+
 // Returns 1 on a hit, 0 on a miss, and -1 (CONS only) when the winner's certificate fails:
 // the caller then walks the reference order instead.
-template <bool STATS, bool FAST, bool CONS = false, typename SRC>
-__device__ __forceinline__ int trace(const SRC& nodes, int n_nodes, const RayK& ray, Hit& h, int& code_out,
+template <bool STATS, bool FAST, bool CONS = false, typename SRC, typename WIN>
+__device__ __forceinline__ int trace(const SRC& nodes, int n_nodes, const RayK& ray, Hit& h, WIN& code_out,
                                      Counters& cnt) {
     float tmax = DEFAULT_RAY_TMAX;
     int best = -1, kind = 0;
@@ -637,7 +651,7 @@ __device__ __forceinline__ int trace(const SRC& nodes, int n_nodes, const RayK& 
         if (!cert_inside(box, ray, tmax) && slab_reject<FAST>(box, with_slab(ray), tmax)) return -1;
     }
     h = hit_attributes(w, ray, tmax, kind);
-    code_out = w.code;
+    put_winner(code_out, w, tmax);
     return 1;
 }
 
@@ -765,9 +779,9 @@ struct WalkState {
 
 // `tree` is the block's LDS copy of the image's first lds_tree_nodes(n_wide) nodes; HYB: the
 // tree is larger (n_wide > LDS_TREE_NODES), so some nodes come from global memory.
-template <bool STATS, int BLK, bool HYB>
+template <bool STATS, int BLK, bool HYB, typename WIN>
 __device__ __forceinline__ int trace_wide(const KParams& p, __amdgpu_buffer_rsrc_t rsrc, int oct, const RayK& ray,
-                                          Hit& h, int& code_out, Counters& cnt, const uint4* tree, WalkState& ws,
+                                          Hit& h, WIN& code_out, Counters& cnt, const uint4* tree, WalkState& ws,
                                           int suspend_at) {
     __shared__ int16_t wstack[CPT_WSTACK * BLK];
     // an LDS-typed pointer: 32-bit ds_read/ds_write addressing (a generic pointer costs a
@@ -962,7 +976,7 @@ __device__ __forceinline__ int trace_wide(const KParams& p, __amdgpu_buffer_rsrc
     leaf_aabb(wn, box);
     if (!cert_inside(box, ray, tmax) && slab_reject<true>(box, with_slab(ray), tmax)) return -1;
     h = hit_attributes(wn, ray, tmax, kind);
-    code_out = wn.code;
+    put_winner(code_out, wn, tmax);
     return 1;
 }
 
@@ -972,14 +986,14 @@ __device__ __forceinline__ int trace_wide(const KParams& p, __amdgpu_buffer_rsrc
 // the binary octant orders testing each leaf where the walk meets it.
 // Returns 1 hit, 0 miss, or 2 when the walk was suspended (only with suspend_at > 0; the
 // lane calls again in a later round with the same ray and `ws`).
-template <bool STATS, bool FAST, bool CONS = false>
+template <bool STATS, bool FAST, bool CONS = false, typename WIN>
 __device__ __forceinline__ int trace_any(__amdgpu_buffer_rsrc_t rsrc, uint32_t base, int n, const RayK& ray, Hit& h,
-                                         int& code, Counters& cnt) {
+                                         WIN& code, Counters& cnt) {
     return trace<STATS, FAST, CONS>(BufSrc{rsrc, base}, n, ray, h, code, cnt);
 }
 
-template <bool STATS, int BLK = WIDE_LANES, bool LDST = false, bool HYB = true>
-__device__ __forceinline__ int trace_segment(const KParams& p, const RayK& rk, bool finite, Hit& h, int& code,
+template <bool STATS, int BLK = WIDE_LANES, bool LDST = false, bool HYB = true, typename WIN>
+__device__ __forceinline__ int trace_segment(const KParams& p, const RayK& rk, bool finite, Hit& h, WIN& code,
                                              Counters& cnt, const uint4* tree, WalkState& ws, int suspend_at) {
     const __amdgpu_buffer_rsrc_t rsrc = node_rsrc(p);
     if (p.ordered && __builtin_expect(finite, 1)) {
@@ -1005,8 +1019,8 @@ __device__ __forceinline__ int trace_segment(const KParams& p, const RayK& rk, b
 }
 
 // The same without suspension (a walk always completes).
-template <bool STATS, int BLK = WIDE_LANES, bool LDST = false>
-__device__ __forceinline__ bool trace_segment(const KParams& p, const RayK& rk, bool finite, Hit& h, int& code,
+template <bool STATS, int BLK = WIDE_LANES, bool LDST = false, typename WIN>
+__device__ __forceinline__ bool trace_segment(const KParams& p, const RayK& rk, bool finite, Hit& h, WIN& code,
                                               Counters& cnt, const uint4* tree = nullptr) {
     WalkState ws;
     ws.active = false;

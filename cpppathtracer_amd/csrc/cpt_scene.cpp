@@ -179,6 +179,14 @@ int upload_scene(cpt_ctx* c) {
     hipStream_t s = c->stream();
     if (!c->lin.empty())
         HIP_TRY(c, hipMemcpyAsync(c->d_nodes, c->lin.data(), c->lin.size() * sizeof(Node), hipMemcpyHostToDevice, s));
+    // the ray queries' table: the object of each reference-order position (a leaf's rank)
+    std::vector<int32_t>& rank_obj = c->rank_obj;   // (a member: it outlives the copy)
+    rank_obj.assign((size_t)c->n_bvh, -1);
+    for (size_t i = 0; i < c->bvh.nodes.size() && c->n_bvh > 0; ++i)
+        if (c->bvh.nodes[i].is_object) rank_obj[c->pos_of_node[i]] = c->bvh.nodes[i].obj;
+    if ((rc = c->d_rank_obj.ensure(c, std::max<size_t>(1, rank_obj.size()))) != CPT_OK) return rc;
+    if (!rank_obj.empty())
+        HIP_TRY(c, hipMemcpyAsync(c->d_rank_obj, rank_obj.data(), rank_obj.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (!c->refit_plan.empty()) {   // the device refit's plan and the boxes as built
         if ((rc = c->d_refit_plan.ensure(c, c->refit_plan.size())) != CPT_OK) return rc;
         if ((rc = c->d_refit_boxes.ensure(c, c->refit_boxes.size())) != CPT_OK) return rc;

@@ -258,6 +258,59 @@ class Renderer:
         self._check(self._L.cpt_last_filter_ms(self._ctx, ctypes.byref(ms)))
         return float(ms.value)
 
+    # -- first-hit queries -----------------------------------------------------------
+    def gbuffer(self, cam, flags=0):
+        """cpt_gbuffer: the first hit of every pixel's centre ray (RayGen at zero lens offset), by
+        the walk of `flags` (CPT_TRAVERSAL_* bits only).  Writes buffers of its own; the
+        accumulator, the RNG states and the aux buffers are untouched.  Asynchronous;
+        read_gbuffer waits."""
+        c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
+        self._check(self._L.cpt_gbuffer(self._ctx, _p(c), int(flags)))
+
+    def read_gbuffer(self):
+        """The last gbuffer's result (cpt_read_gbuffer): {"id" [npix] int32 (object index in
+        set_scene's order, -1 = miss), "t" [npix] (1e30 on a miss), "normal" [npix, 3] (-dir on a
+        miss), "albedo" [npix, 3] (0 on a miss)}."""
+        out = {"id": np.zeros(self.npix, dtype=np.int32), "t": np.zeros(self.npix, dtype=np.float32),
+               "normal": np.zeros((self.npix, 3), dtype=np.float32), "albedo": np.zeros((self.npix, 3), dtype=np.float32)}
+        self._check(self._L.cpt_read_gbuffer(self._ctx, _p(out["id"]), _p(out["t"]), _p(out["normal"]), _p(out["albedo"]),
+                                             self.npix))
+        return out
+
+    def trace_rays(self, origins, dirs, tmin=None, flags=0):
+        """cpt_trace_rays: the first hit of each ray (origins, dirs [n, 3]; tmin [n] or None = 0);
+        directions are used as given, not normalised.  Needs only a scene.  Returns {"id" [n]
+        int32, "t" [n], "normal" [n, 3]} with gbuffer's miss conventions.  Synchronous."""
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError(f"trace_rays: {o.shape[0]} origins for {d.shape[0]} directions")
+        n = o.shape[0]
+        tm = None
+        if tmin is not None:
+            tm = np.ascontiguousarray(tmin, dtype=np.float32).reshape(-1)
+            if tm.size != n:
+                raise ValueError(f"trace_rays: {tm.size} tmin values for {n} rays")
+        out = {"id": np.zeros(n, dtype=np.int32), "t": np.zeros(n, dtype=np.float32),
+               "normal": np.zeros((n, 3), dtype=np.float32)}
+        self._check(self._L.cpt_trace_rays(self._ctx, n, _p(o), _p(d), _p(tm), int(flags), _p(out["id"]), _p(out["t"]),
+                                           _p(out["normal"])))
+        return out
+
+    def pick(self, cam, x, y, flags=0):
+        """cpt_pick: (object index or -1, distance) under pixel (x, y) of the image: gbuffer's id
+        and t of that pixel, by one ray.  Synchronous."""
+        c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
+        obj, t = ctypes.c_int32(-1), ctypes.c_float(0)
+        self._check(self._L.cpt_pick(self._ctx, _p(c), int(x), int(y), int(flags), ctypes.byref(obj), ctypes.byref(t)))
+        return int(obj.value), np.float32(t.value)
+
+    def last_query_ms(self) -> float:
+        """Device time of the last gbuffer, trace_rays or pick kernel (HIP events); waits for it."""
+        ms = ctypes.c_float(0)
+        self._check(self._L.cpt_last_query_ms(self._ctx, ctypes.byref(ms)))
+        return float(ms.value)
+
     def tile_costs(self, cam, passes, max_depth, ordered=True):
         """The cost schedule's pilot alone (cpt_tile_costs): the work of each 8x8 tile's heaviest
         pixel (the maximum over the tile's pixels, not their sum) over `passes` passes from the

@@ -4,7 +4,10 @@
 //   cpt_headless [--scene s3|s4|s1000] [--width W] [--height H] [--spp N] [--depth D] [--seed S]
 //                [--out radiance.bin] [--dispatch K --bgra frame.bin] [--pfm image.pfm]
 //                [--texture file.ppm|file.cptex] [--dump-scene objects.bin] [--devices N]
-//                [--objects N] [--animate K]
+//                [--objects N] [--animate K] [--pick X,Y]
+//
+// --pick X,Y prints the object (AddObject index, -1 = sky) under pixel (X, Y) of the image and its
+// distance (PathTracer::Pick: one centre ray, no render), then exits.
 //
 // --devices N row-tiles the image over N contexts (PathTracer::SetDevices: device i % visible
 // devices, so N > the GPU count puts several tiles on one GPU) and gathers each pass's tiles
@@ -146,7 +149,7 @@ void on_frame(uint8_t* data, int width, int height, void* param) {
 }  // namespace
 
 int main(int argc, char** argv) {
-    std::string scene = "s4", out, bgra_out, pfm, texture, dump_scene;
+    std::string scene = "s4", out, bgra_out, pfm, texture, dump_scene, pick;
     int W = 64, H = 36, spp = 2, depth = 8, dispatch = 0, devices = 1, n_objects = 1000, animate = 0;
     unsigned long long seed = 1234;
     // --adaptive REL: --spp is the most passes a pixel gets; tiles stop once their pixels'
@@ -181,6 +184,7 @@ int main(int argc, char** argv) {
         else if (k == "--devices") devices = std::stoi(v);
         else if (k == "--objects") n_objects = std::stoi(v);
         else if (k == "--animate") animate = std::stoi(v);
+        else if (k == "--pick") pick = v;
         else if (k == "--adaptive") adaptive = std::stof(v);
         else if (k == "--min-spp") min_spp = std::stoi(v);
         else if (k == "--batch") batch = std::stoi(v);
@@ -236,6 +240,16 @@ int main(int argc, char** argv) {
         f.write(reinterpret_cast<const char*>(built.data()), (std::streamsize)(built.size() * sizeof(cpt_object)));
         printf("dumped %zu objects\n", built.size());
         return f ? 0 : 1;
+    }
+
+    if (!pick.empty()) {
+        int px = 0, py = 0;
+        if (sscanf(pick.c_str(), "%d,%d", &px, &py) != 2) { fprintf(stderr, "--pick wants X,Y\n"); return 2; }
+        float t = 0.f;
+        const int object = tracer.Pick(px, py, &t);
+        if (object < 0 && !tracer.LastError().empty()) { fprintf(stderr, "Pick: %s\n", tracer.LastError().c_str()); return 1; }
+        printf("pick (%d, %d): object %d, t %.9g\n", px, py, object, (double)t);
+        return 0;
     }
 
     if (dispatch > 0) {

@@ -11,7 +11,8 @@
 // Additions the headless configs need (the reference has no setters for these):
 //   SetMaxRecursionDepth, SetSeed, SetDevice, SetDevices (row tiling over several GPUs),
 //   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance,
-//   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, GetStats, Stop.
+//   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
+//   GetStats, Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -90,6 +91,17 @@ public:
     // Last display frame (denoised running mean), BGRA8[width*height*4].
     bool ReadFrameBGRA(std::vector<uint8_t>& bgra);
     bool SaveRadiancePFM(const std::string& path);
+    // The object under pixel (x, y) of the current camera's image (cpt_pick): its AddObject index,
+    // or -1 for the sky, a pixel outside the image or a failure (LastError() then holds the
+    // message); *t, when given, gets the hit distance (1e30 on a miss).  The ray is the pixel's
+    // centre ray (no lens sample); pending UpdateObjects are refit first, as Render does.  With
+    // SetDevices the ray runs on the first tile's context.  The camera's sample index, the
+    // accumulator and the RNG are left as they are.
+    int Pick(int x, int y, float* t = nullptr);
+    // The G-buffer of the current camera's full frame (cpt_gbuffer, row-major, y down): object
+    // index (-1: sky), hit distance, normal and albedo (float[width*height*3] each) per pixel.
+    bool ReadGBuffer(std::vector<int32_t>& id, std::vector<float>& t, std::vector<float>& normal3,
+                     std::vector<float>& albedo3);
     bool GetStats(cpt_stats* out);
     void Stop();                                 // stop the render thread (also in ~PathTracer)
     const std::string& LastError() const { return err_; }

@@ -368,6 +368,44 @@ int cpt_filter_prepare_host(size_t npix, const float* accum_rgba, const float* m
                             uint8_t* out_valid);
 int cpt_filter_level_host(int width, int height, int step, const float* in_rgbv, const float* normal3, const uint8_t* valid,
                           float sigma_l, int normal_sharpness_log2, float* out_rgbv);
+/* First-hit queries (additions: the reference has no counterpart; its only first-hit data are the
+ * normal and the constant depth 1e30 that SamplePixel writes, path_tracer.cu:172-174, and nothing
+ * in it names the object a ray hits).  All of them walk SceneBVH::TraceRay
+ * (bvh.cu:167-205) exactly as cpt_render's first segment does under the same `flags`, of which only
+ * the CPT_TRAVERSAL_* bits are accepted (any other bit: CPT_ERR_INVALID_ARG).  They read the scene
+ * and the camera and write none of the accumulator, RNG states, aux buffers, moments, filter planes
+ * or display state; no RNG draw is made.  Per ray: the object's index in cpt_set_scene's (AddObject)
+ * order, the winning intersector's distance t, the normal the reference's intersector forms, and
+ * the material's GetKd(0, 0) (material.cu:11-18).  A miss gives -1, t = 1e30 (DEFAULT_RAY_TMAX), the
+ * normal -dir (the integrator's Miss convention) and albedo 0.  The indices stay AddObject indices
+ * through cpt_update_objects and cpt_update_objects_rebuild.  A missing scene (or, for cpt_gbuffer
+ * and cpt_pick, frame): CPT_ERR_STATE; a NULL required pointer: CPT_ERR_INVALID_ARG; nothing is
+ * written in either case.
+ *
+ * cpt_gbuffer: the G-buffer of the context's pixels, pixel i = (i % width, rows[i / width]) as in
+ * cpt_set_frame.  A pixel's ray is RayGen's (motional_camera.cu:202-213) with the lens offset taken
+ * as zero: the ray cpt_render shoots when lens_radius == 0, and the centre ray of a defocused
+ * camera.  The camera must have the frame's size.  The result lives in buffers of its own on the
+ * frame, allocated at the first call and dropped by cpt_set_frame.  Asynchronous, on the context's
+ * stream; CPT_ERR_STATE while an adaptive render is pending. */
+int cpt_gbuffer(cpt_ctx* ctx, const cpt_camera* cam, uint32_t flags);
+/* The last cpt_gbuffer's result (CPT_ERR_STATE if none since cpt_set_frame): id [n_rows*width], t
+ * [n_rows*width], normal3 and albedo3 [n_rows*width][3]; any may be NULL.  capacity_pixels below
+ * n_rows*width: CPT_ERR_INVALID_ARG, nothing written.  Waits. */
+int cpt_read_gbuffer(cpt_ctx* ctx, int32_t* id, float* t, float* normal3, float* albedo3, size_t capacity_pixels);
+/* n rays from host arrays origin3 / dir3 [n][3] and tmin [n] (NULL: 0 for every ray) into the host
+ * arrays id [n], t [n] and normal3 [n][3].  The direction is used as given, not normalised, as
+ * TraceRay does (t is in units of its length; a miss's normal is -dir as given); tmax is 1e30.
+ * Needs only a scene.  Synchronous; the device staging is sized before the launch. */
+int cpt_trace_rays(cpt_ctx* ctx, size_t n, const float* origin3, const float* dir3, const float* tmin, uint32_t flags,
+                   int32_t* id, float* t, float* normal3);
+/* The object under pixel (x, y) of the image (0 <= x < width, 0 <= y < height, else
+ * CPT_ERR_INVALID_ARG) and, when t is not NULL, its distance: cpt_gbuffer's id and t of that
+ * pixel, by one ray.  *object = -1 and *t = 1e30 on a miss.  Synchronous. */
+int cpt_pick(cpt_ctx* ctx, const cpt_camera* cam, int x, int y, uint32_t flags, int32_t* object, float* t);
+/* Device time of the last cpt_gbuffer, cpt_trace_rays or cpt_pick kernel (HIP events on the
+ * context's stream); waits for it. */
+int cpt_last_query_ms(cpt_ctx* ctx, float* ms);
 /* Device-to-device copy of the accumulator (e.g. into an RCCL send buffer), ordered against the
  * caller's HIP stream `caller_stream` (NULL: the null stream) without blocking the host: the
  * context's stream first waits for the work queued on caller_stream so far (a fill of dst, a
