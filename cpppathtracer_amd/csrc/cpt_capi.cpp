@@ -138,7 +138,7 @@ int cpt_create(int device, cpt_ctx** out) {
     for (DevEvent* ev : {&c->t_render.t0, &c->t_render.t1, &c->ev_main, &c->t_display.t0, &c->t_display.t1, &c->t_filter.t0,
                           &c->t_filter.t1, &c->t_query.t0, &c->t_query.t1})
         if (e == hipSuccess) e = ev->create();
-    for (DevEvent* ev : {&c->ev_ready, &c->ev_gathered, &c->ev_caller, &c->ev_copied, &c->ev_round})
+    for (DevEvent* ev : {&c->ev_ready, &c->ev_gathered, &c->ev_caller, &c->ev_copied, &c->ev_round, &c->ev_switch})
         if (e == hipSuccess) e = ev->create(hipEventDisableTiming);
     if (e == hipSuccess) e = c->h_ad_words.alloc(4);
     if (e == hipSuccess) e = c->d_stats.alloc(128);   // [64..128) execdiag
@@ -174,7 +174,18 @@ const char* cpt_last_error(const cpt_ctx* c) { return c ? c->err.c_str() : g_cre
 
 int cpt_set_stream(cpt_ctx* c, void* s) {
     if (!c) return CPT_ERR_INVALID_ARG;
+    const hipStream_t before = c->stream();
     c->user_stream = (hipStream_t)s;
+    const hipStream_t after = c->stream();
+    if (after == before) return CPT_OK;
+    // The context's buffers (accumulator, RNG planes, the dequeue and error words of d_work) have one
+    // writer at a time only while its work runs in the order of the calls: what is queued on the
+    // stream being left runs before anything queued on the new one from here on, by an event, with
+    // no host wait (as copy_ordered).  sync_checked drains the new stream alone, and that now
+    // includes the wait for this event.
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventRecord(c->ev_switch, before));
+    HIP_TRY(c, hipStreamWaitEvent(after, c->ev_switch, 0));
     return CPT_OK;
 }
 

@@ -254,6 +254,7 @@ struct cpt_ctx {
     DevEvent ev_gathered; // a gather's destination: the stitch done
     DevEvent ev_caller;   // a device copy's caller stream: its queued work
     DevEvent ev_copied;   // a device copy: done on the context's stream
+    DevEvent ev_switch;   // cpt_set_stream: the work queued on the stream being left
     // consolidation test hooks (cpt_set_debug_consolidation)
     uint32_t dbg = 0;
     bool force_staged_gather = false;   // gather test hook (cpt_set_debug_gather)

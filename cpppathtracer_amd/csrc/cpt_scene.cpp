@@ -469,6 +469,10 @@ int cpt_set_env_texture(cpt_ctx* c, const uint8_t* rgba, int logical_width, int 
     if (logical_width <= 0 || height <= 0 || valid_cols < 0 || valid_cols > logical_width || (valid_cols > 0 && !rgba))
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_set_env_texture: bad geometry %dx%d cols %d", logical_width, height, valid_cols);
     HIP_TRY(c, hipSetDevice(c->device));
+    // a render queued without CPT_RENDER_SYNC still fetches the sky from d_env: ensure() keeps an
+    // allocation that is large enough, and the blocking copy below is ordered on the null stream
+    // only, which the context's non-blocking stream does not wait for (as cpt_write_accum)
+    HIP_TRY(c, hipStreamSynchronize(c->stream()));
     size_t n = (size_t)valid_cols * height;
     int rc = c->d_env.ensure(c, std::max<size_t>(1, n));
     if (rc != CPT_OK) return rc;
@@ -488,6 +492,10 @@ int cpt_bind_texture(cpt_ctx* c, uint64_t handle, const uint8_t* rgba, int logic
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_bind_texture: bad geometry %dx%d cols %d or mode %d/%d", logical_width,
                     height, valid_cols, address_mode, filter_mode);
     HIP_TRY(c, hipSetDevice(c->device));
+    // No wait for the context's stream is needed here.  The texels go into a fresh buffer that no
+    // queued work knows; the one they replace is released by hipFree, which waits for the device;
+    // and no render reads texels: k_prepare_materials samples them once (upload_scene, which
+    // queues it on the context's stream behind a render in flight and waits for it).
     const size_t n = (size_t)valid_cols * height;
     DevBuf<uint32_t> d;
     if (int rc = d.ensure(c, std::max<size_t>(1, n))) return rc;

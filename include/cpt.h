@@ -182,7 +182,14 @@ int cpt_create(int device, cpt_ctx** out);
 int cpt_destroy(cpt_ctx* ctx);
 /* Last error message of ctx (or of the last failed cpt_create when ctx is NULL). */
 const char* cpt_last_error(const cpt_ctx* ctx);
-/* Launch on `hip_stream` (a hipStream_t) instead of the context's own stream; NULL restores it. */
+/* Launch on `hip_stream` (a hipStream_t) instead of the context's own stream; NULL restores it.
+ * Ordering rule: when the call changes the stream in use, everything the context has queued on the
+ * stream it leaves runs before anything it queues on the new one afterwards (an event recorded on
+ * the old stream that the new one waits for; no host wait), so a render in flight and the next
+ * call never share the accumulator, the RNG planes or the dequeue word, and a synchronising call
+ * after the switch also waits for the old stream's work.  The stream being left must still exist
+ * at the call (restore NULL before destroying a stream of yours).  Naming the stream already in
+ * use changes nothing. */
 int cpt_set_stream(cpt_ctx* ctx, void* hip_stream);
 
 /* Host-side MotionalCamera::GetCopy: computes the basis and corner vectors, increments
@@ -220,7 +227,10 @@ int cpt_bvh_build_host(const cpt_object* objs, int n_objs, float* boxes, int32_t
 
 /* Environment map, RGBA8 rows of `valid_cols` texels (the reference uploads only
  * logical_width/4 texels per row, textures.cu:32-33; texels at x >= valid_cols read 0).
- * Sampler: normalized coords, mirror addressing, bilinear, c/255 (textures.cu:36-44). */
+ * Sampler: normalized coords, mirror addressing, bilinear, c/255 (textures.cu:36-44).
+ * Ordering rule: waits for the context's queued work before the texels are replaced, so a render
+ * launched without CPT_RENDER_SYNC keeps the sky it was launched with, and the next one has the
+ * new sky. */
 int cpt_set_env_texture(cpt_ctx* ctx, const uint8_t* rgba, int logical_width, int height, int valid_cols);
 
 /* cudaTextureAddressMode / cudaTextureFilterMode values of AddTexByFile's arguments. */

@@ -15,9 +15,13 @@ set_scene in between.  Everything is bit-exact, against the oracle's refit
 * an update queued behind a render in flight, and the argument checks.
 
 test_edit_fuzz.py checks on the CPU that the sequences are what they are meant to be."""
+import time
+
 import edit_fuzz as ef
 import numpy as np
 import pytest
+from test_gpu_async_order import SPP as ASYNC_SPP
+from test_gpu_async_order import assert_overlap
 from test_gpu_fuzz_parity import SHORT_PATHS
 from test_gpu_parity import _check_stats, _kw, _timed
 
@@ -33,19 +37,21 @@ SEED = 5
 _ORACLE = {}
 
 
-def _oracle(oracle_mod, sky, name, f, path):
+def _oracle(oracle_mod, sky, name, f, path, spp=None):
     """The oracle's (accum, rng, stats) after frames[:f + 1] (f = -1: the scene as built); for an
     ordered path the stats carry the diagnostic walk's under "walk", as _check_stats expects.  The
-    renders do not depend on the path, so they are made once."""
-    acc, rng, st, walk = _oracle_renders(oracle_mod, sky, name, f)
+    renders do not depend on the path, so they are made once.  spp: the passes, when they are not
+    the family's (ef.PARAMS)."""
+    acc, rng, st, walk = _oracle_renders(oracle_mod, sky, name, f, spp)
     return acc, rng, (dict(st, walk=walk) if _kw(path)["ordered"] else dict(st))
 
 
-def _oracle_renders(oracle_mod, sky, name, f):
-    if (name, f) in _ORACLE:
-        return _ORACLE[(name, f)]
+def _oracle_renders(oracle_mod, sky, name, f, spp=None):
+    if (name, f, spp) in _ORACLE:
+        return _ORACLE[(name, f, spp)]
     family, objs, cam, frames = SEQ[name]
-    spp, depth = ef.PARAMS[family]
+    depth = ef.PARAMS[family][1]
+    spp = spp or ef.PARAMS[family][0]
     cam = camera_get_copy(cam)
     W, H = int(cam["width"]), int(cam["height"])
     rows = np.arange(H, dtype=np.int32)
@@ -63,8 +69,9 @@ def _oracle_renders(oracle_mod, sky, name, f):
         out.append((acc, rng, st))
     np.testing.assert_array_equal(out[1][0].view(np.uint32), out[0][0].view(np.uint32))
     np.testing.assert_array_equal(out[1][1], out[0][1])
-    _ORACLE[(name, f)] = (out[0][0], out[0][1], out[0][2], out[1][2])
-    return _ORACLE[(name, f)]
+    key = (name, f, None if spp == ef.PARAMS[family][0] else spp)
+    _ORACLE[key] = (out[0][0], out[0][1], out[0][2], out[1][2])
+    return _ORACLE[key]
 
 
 def _setup(gpu, sky, name):
@@ -282,18 +289,25 @@ def test_device_bytes(gpu, name):
 @pytest.mark.parametrize("name", [n for n in NAMES if SEQ[n][0] == "all_dirty"])
 def test_update_behind_a_render_in_flight(gpu, oracle_mod, sky, name):
     """render(sync=False), then at once an update that dirties every leaf: the accumulator is the
-    oracle's image of the scene BEFORE the edit, and the next render its image after."""
+    oracle's image of the scene BEFORE the edit, and the next render its image after.  With the
+    passes and the overlap condition of test_gpu_async_order.py: at least three quarters of the
+    render were still ahead when the update began."""
     path = "megakernel:ordered"
-    cam, spp, depth = view = _setup(gpu, sky, name)
+    cam, _, depth = _setup(gpu, sky, name)
+    view = cam, ASYNC_SPP, depth
     gpu.init_rng(SEED)
-    gpu.render(cam, spp, depth, sync=False, **_kw(path))
+    gpu.synchronize()
+    t_launch = time.perf_counter()
+    gpu.render(cam, ASYNC_SPP, depth, sync=False, consolidate=False, **_kw(path))
+    t_call = time.perf_counter()
     _update(gpu, SEQ[name][3][0])
     acc, rng = gpu.read_accum(), gpu.read_rng()
-    oa, orng, _ = _oracle(oracle_mod, sky, name, -1, path)
+    assert_overlap(name, t_launch, t_call, gpu.last_render_ms())
+    oa, orng, _ = _oracle(oracle_mod, sky, name, -1, path, ASYNC_SPP)
     np.testing.assert_array_equal(rng, orng)
     np.testing.assert_array_equal(acc.view(np.uint32), oa.view(np.uint32))
     ga, gr, gs = _render(gpu, view, path)
-    oa, orng, os_ = _oracle(oracle_mod, sky, name, 0, path)
+    oa, orng, os_ = _oracle(oracle_mod, sky, name, 0, path, ASYNC_SPP)
     np.testing.assert_array_equal(gr, orng)
     _check_stats(gs, os_, path)
     np.testing.assert_array_equal(ga.view(np.uint32), oa.view(np.uint32))
