@@ -190,7 +190,7 @@ int cpt::ctx::consolidation_slab(cpt_ctx* c, cpt::KParams& p, int spp, uint32_t 
                        frame_px <= 4u * grid_lanes);
     if (!cons || spp <= 1) return CPT_OK;
     const size_t cap = 3u * 256u * cus;
-    if (int rc = c->d_resume.ensure(c, 5 * cap)) return rc;
+    if (int rc = c->d_resume.ensure(c, cpt::HO_SLOT_QUADS * cap)) return rc;
     p.resume = c->d_resume;
     p.resume_cap = cap;
     return CPT_OK;

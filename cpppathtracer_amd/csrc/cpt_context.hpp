@@ -225,7 +225,7 @@ struct cpt_ctx {
     DevBuf<uint32_t> d_jumps;    // rng init: the XORWOW jump tables
     DevBuf<unsigned long long> d_stats;
     DevBuf<uint32_t> d_work;
-    DevBuf<uint4> d_resume;      // tail consolidation: handed-over chains (5 x uint4 each)
+    DevBuf<uint4> d_resume;      // tail consolidation: handed-over chains (HO_SLOT_QUADS x uint4 each)
     float last_kernel_ms = 0.f;
     int last_launches = 0;
     // row-tile gather (cpt_gather_rows): per source context, the frame row each of its rows goes

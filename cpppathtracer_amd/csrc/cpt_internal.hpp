@@ -17,6 +17,9 @@ namespace cpt {
 constexpr int LDS_TREE_NODES = 512;
 __host__ __device__ __forceinline__ int lds_tree_nodes(int n_wide) { return n_wide < LDS_TREE_NODES ? n_wide : LDS_TREE_NODES; }
 
+// uint4s of KParams::resume per handed-over chain (k_megakernel's hand-over payload: 17 words).
+constexpr int HO_SLOT_QUADS = 5;
+
 // Camera snapshot as the kernel needs it (the reference passes the whole MotionalCamera by
 // value in PathTracerParams, path_tracer.cu:14-27; only these fields are read by RayGen).
 struct CamK {
@@ -58,7 +61,7 @@ struct KParams {
     int lanes;              // lanes per wave that take pixels (64; fewer: DIAGNOSTIC CPT_LANES_PER_WAVE)
     int replicate;          // lanes per taken pixel (1; more: DIAGNOSTIC CPT_REPLICATE, identical copies)
     // Tail consolidation (LDS walk only; nullptr: off): slabs of chains handed over at a pass
-    // boundary by retiring waves, 5 x uint4 per chain, ho_slots chains per workgroup.
+    // boundary by retiring waves, HO_SLOT_QUADS x uint4 per chain, ho_slots chains per workgroup.
     uint4* resume;
     size_t resume_cap;      // chains (all workgroups)
     // Sticky device error word (CPT_DEVERR_*), or-ed by a kernel that had to abandon work; the
@@ -74,6 +77,11 @@ struct KParams {
     // dequeued (tiles still noisy); 0 = every tile of the frame, as every other launch passes.
     uint32_t n_active;
 };
+
+// The wide walk (the ordered walk on a 4-wide tree) runs in the LDS kernels: the image's first
+// LDS_TREE_NODES nodes in LDS, the rest of a larger tree from global memory.  The launchers pick
+// the LDST kernels by this, and trace_segment's LDST branch walks by it.
+__host__ __device__ __forceinline__ bool use_lds_tree(const KParams& p) { return p.ordered == 1 && p.n_wide > 0; }
 
 // Device error bits (KParams::error).
 enum : uint32_t {

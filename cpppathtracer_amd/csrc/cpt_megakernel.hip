@@ -11,7 +11,9 @@
 //                        69-70, 103-104; here because its register assignment depends on the unit
 //
 // Reference semantics per function are cited inline; DESIGN.md has the data layout and the
-// roofline of each kernel.
+// roofline of each kernel.  Out of the round as named pieces so far: HoPayload (the
+// hand-over slot's one layout), finish_pixel, and in cpt_path.hpp stage_wide_tree, ray_is_finite,
+// load_rng / store_rng and flush_walk_counters; refill, hand-over queue and sky are still inline.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -78,23 +80,10 @@ struct Lane {
     // render, if it accumulates; p.accumulate is read after the RNG loads are issued)
     template <bool ACC>
     __device__ __forceinline__ void load(const KParams& p, size_t npix) {
-        s.v0 = p.rng[pix];
-        s.v1 = p.rng[npix + pix];
-        s.v2 = p.rng[2 * npix + (size_t)pix];
-        s.v3 = p.rng[3 * npix + (size_t)pix];
-        s.v4 = p.rng[4 * npix + (size_t)pix];
-        s.d = p.rng[5 * npix + (size_t)pix];
+        load_rng(p, npix, pix, s);
         const float4 a = (p.accumulate && ACC) ? p.accum[pix] : make_float4(0.f, 0.f, 0.f, 0.f);
         sum = mk(a.x, a.y, a.z);
         passes = a.w;
-    }
-    __device__ __forceinline__ void store_rng(const KParams& p, size_t npix) const {
-        p.rng[pix] = s.v0;
-        p.rng[npix + pix] = s.v1;
-        p.rng[2 * npix + (size_t)pix] = s.v2;
-        p.rng[3 * npix + (size_t)pix] = s.v3;
-        p.rng[4 * npix + (size_t)pix] = s.v4;
-        p.rng[5 * npix + (size_t)pix] = s.d;
     }
 };
 
@@ -112,6 +101,61 @@ struct PendingSky {
     __device__ __forceinline__ v3 rad() const { return mk(q[3 * BLK], q[4 * BLK], q[5 * BLK]); }
     __device__ __forceinline__ v3 att() const { return mk(q[6 * BLK], q[7 * BLK], q[8 * BLK]); }
 };
+
+// A hand-over slot's payload, the chain at a pass boundary (HO_SLOT_QUADS x 16 B in the slab):
+// pix, xy, the six RNG words, sum, passes, the first normal and a spare word (AUX only), passes
+// left; moved by coherent (sc1) stores / loads of the words in use, in word order.
+struct HoPayload {
+    static constexpr int WORDS = 17;
+    static_assert(WORDS <= 4 * HO_SLOT_QUADS, "a slot holds the payload");
+    template <bool AUX> static constexpr bool used(int k) { return AUX || k < 12 || k == 16; }
+    template <bool AUX>
+    __device__ __forceinline__ static void store(uint32_t* e, const Lane& L, const v3& first_normal) {
+        const uint32_t w[WORDS] = {L.pix, L.xy, L.s.v0, L.s.v1, L.s.v2, L.s.v3, L.s.v4, L.s.d,
+                                   __float_as_uint(L.sum.x), __float_as_uint(L.sum.y), __float_as_uint(L.sum.z),
+                                   __float_as_uint(L.passes), __float_as_uint(first_normal.x),
+                                   __float_as_uint(first_normal.y), __float_as_uint(first_normal.z), 0u, (uint32_t)L.left};
+#pragma unroll
+        for (int k = 0; k < WORDS; ++k)
+            if (used<AUX>(k)) st_coherent(e + k, w[k]);
+    }
+    template <bool AUX>
+    __device__ __forceinline__ static void load(const uint32_t* e, Lane& L, v3& first_normal) {
+        uint32_t w[WORDS];
+#pragma unroll
+        for (int k = 0; k < WORDS; ++k) w[k] = used<AUX>(k) ? ld_coherent(e + k) : 0u;
+        L.pix = w[0]; L.xy = w[1]; L.s.v0 = w[2]; L.s.v1 = w[3]; L.s.v2 = w[4]; L.s.v3 = w[5]; L.s.v4 = w[6]; L.s.d = w[7];
+        L.sum = mk(__uint_as_float(w[8]), __uint_as_float(w[9]), __uint_as_float(w[10]));
+        L.passes = __uint_as_float(w[11]);
+        if (AUX) first_normal = mk(__uint_as_float(w[12]), __uint_as_float(w[13]), __uint_as_float(w[14]));
+        L.left = (int)w[16];
+    }
+};
+__device__ __forceinline__ uint32_t* ho_slot(uint4* slab, uint32_t slot) {
+    return reinterpret_cast<uint32_t*>(slab + HO_SLOT_QUADS * (size_t)slot);
+}
+
+// A finished chain: the pilot's cost (PROBE), or the write-back (path_tracer.cu:172-174).
+template <bool AUX, bool PROBE>
+__device__ __forceinline__ void finish_pixel(const KParams& p, const Lane& L, const v3& first_normal, uint32_t work_at_take,
+                                             const Counters& cnt, size_t npix, uint32_t max_depth) {
+    if (PROBE) {
+        // the tile's key is its heaviest pixel's work, not the tile's sum (round 6): one long
+        // chain in an otherwise light tile must start with the first tiles, not in the tail
+        // (tools/timeline.py: C5 N = 8, the rank's last quarter ran a few hundred such chains)
+        atomicMax(&p.tile_cost[L.tile], cnt.segments + cnt.nodes + cnt.prims - work_at_take);
+        return;
+    }
+    execdiag::lanes(p.stats + 64, 11);
+    p.accum[L.pix] = make_float4(L.sum.x, L.sum.y, L.sum.z, L.passes);
+    if (AUX && p.spp > 0) {
+        p.normal[3 * (size_t)L.pix + 0] = first_normal.x;
+        p.normal[3 * (size_t)L.pix + 1] = first_normal.y;
+        p.normal[3 * (size_t)L.pix + 2] = first_normal.z;
+        p.depth[L.pix] = max_depth > 0 ? DEFAULT_RAY_TMAX : 0.f;   // a18
+    }
+    store_rng(p, npix, L.pix, L.s);
+}
 
 __device__ __forceinline__ bool decode_pixel(const KParams& p, uint32_t id, int& x, int& ri, uint32_t& tile) {
     tile = id >> 6;
@@ -138,11 +182,7 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
     constexpr int BLK = mk_block<LDST>();
     __shared__ uint4 s_tree[LDST ? LDS_TREE_NODES * 7 : 1];
     pooldiag::init();
-    if (LDST) {
-        const uint4* src = reinterpret_cast<const uint4*>(p.nodes + wide_image_base(p));
-        for (int i = threadIdx.x; i < 7 * lds_tree_nodes(p.n_wide); i += BLK) s_tree[i] = src[i];
-        __syncthreads();
-    }
+    if (LDST) stage_wide_tree<BLK>(s_tree, p);
     const int lane = threadIdx.x & 63;
     const size_t npix = (size_t)p.n_rows * p.width;
     // (an adaptive render's later rounds dequeue only the first n_active tiles of p.tile_order)
@@ -178,7 +218,7 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
     __shared__ uint8_t s_qflag[QS];          // slot published
     const bool cons = CONS && (size_t)(blockIdx.x + 1) * QS <= p.resume_cap;
     if (CONS && !cons && threadIdx.x == 0) atomicOr(p.error, CPT_DEVERR_RESUME_CAP);   // runs unconsolidated
-    uint4* const qslab = cons ? p.resume + 5 * (size_t)blockIdx.x * QS : nullptr;
+    uint4* const qslab = cons ? p.resume + HO_SLOT_QUADS * (size_t)blockIdx.x * QS : nullptr;
     volatile uint32_t* const vq = s_q;
     const uint32_t level = __builtin_amdgcn_readfirstlane((uint32_t)(threadIdx.x >> 8));
     bool retiring = false;       // wave-uniform: hand every chain over at its next pass end
@@ -399,22 +439,7 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
                         atomicOr(p.error, CPT_DEVERR_PUBLISH_TIMEOUT);
                         atomicSub(&s_q[2], 1u);
                     } else if (((need >> lane) & 1ull) && rank < n) {
-                        const uint32_t slot = h + rank;
-                        const uint32_t* e = reinterpret_cast<const uint32_t*>(qslab + 5 * (size_t)slot);
-                        auto ld4 = [&](int q) {
-                            return make_uint4(ld_coherent(e + 4 * q), ld_coherent(e + 4 * q + 1), ld_coherent(e + 4 * q + 2),
-                                              ld_coherent(e + 4 * q + 3));
-                        };
-                        const uint4 e0 = ld4(0), e1 = ld4(1), e2 = ld4(2), e3 = AUX ? ld4(3) : make_uint4(0u, 0u, 0u, 0u);
-                        const uint32_t left = ld_coherent(e + 16);
-                        L.pix = e0.x; L.xy = e0.y; L.s.v0 = e0.z; L.s.v1 = e0.w;
-                        L.s.v2 = e1.x; L.s.v3 = e1.y; L.s.v4 = e1.z; L.s.d = e1.w;
-                        L.sum = mk(__uint_as_float(e2.x), __uint_as_float(e2.y), __uint_as_float(e2.z));
-                        L.passes = __uint_as_float(e2.w);
-                        if (AUX) {
-                            first_normal = mk(__uint_as_float(e3.x), __uint_as_float(e3.y), __uint_as_float(e3.z));
-                        }
-                        L.left = (int)left;
+                        HoPayload::load<AUX>(ho_slot(qslab, h + rank), L, first_normal);
                         busy = true;
                         begin = true;
                     }
@@ -453,8 +478,7 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
             if (COUNT && !ws.active) cnt.segments++;
             execdiag::lanes(p.stats + 64, 12);
             const RayK rk = make_rayk(ray);
-            const bool finite_ray = !(ray.o.x != ray.o.x || ray.o.y != ray.o.y || ray.o.z != ray.o.z ||
-                                      ray.d.x != ray.d.x || ray.d.y != ray.d.y || ray.d.z != ray.d.z);
+            const bool finite_ray = ray_is_finite(ray);
             tr = trace_segment<COUNT, BLK, LDST, HYB>(p, rk, finite_ray, h, code, cnt, s_tree, ws, LDST ? SUSPEND_AT : 0);
         }
         stamps::lap(3);
@@ -567,46 +591,19 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
                 base = __shfl(base, leader);
                 if (hand_over) {
                     execdiag::lanes(p.stats + 64, 14);
-                    const uint32_t slot = base + lane_rank(ho);
-                    {   // slot < QS (ho_slots)
-                        uint32_t* e = reinterpret_cast<uint32_t*>(qslab + 5 * (size_t)slot);
-                        const uint32_t w[20] = {L.pix, L.xy, L.s.v0, L.s.v1, L.s.v2, L.s.v3, L.s.v4, L.s.d,
-                                                __float_as_uint(L.sum.x), __float_as_uint(L.sum.y), __float_as_uint(L.sum.z),
-                                                __float_as_uint(L.passes), __float_as_uint(first_normal.x),
-                                                __float_as_uint(first_normal.y), __float_as_uint(first_normal.z),
-                                                0u, (uint32_t)L.left, 0u, 0u, 0u};
-#pragma unroll
-                        for (int k = 0; k < 17; ++k)
-                            if (AUX || k < 12 || k == 16) st_coherent(e + k, w[k]);
-                        wait_stores();   // the payload is in memory before the flag
-                        if (!(p.dbg & 2u)) *(volatile uint8_t*)(s_qflag + slot) = 1;
-                        busy = false;
-                    }
+                    const uint32_t slot = base + lane_rank(ho);   // < QS (ho_slots)
+                    HoPayload::store<AUX>(ho_slot(qslab, slot), L, first_normal);
+                    wait_stores();   // the payload is in memory before the flag
+                    if (!(p.dbg & 2u)) *(volatile uint8_t*)(s_qflag + slot) = 1;
+                    busy = false;
                     hand_over = false;
                 }
             }
         }
         bool finished = false;
         if (busy && L.left == 0) {
-            const KParams& p = kernarg_params();   // cold fields (see the refill)
-            if (PROBE) {
-                // ---- pilot: the pixel's work goes to its tile's cost ----------------------
-                // the tile's key is its heaviest pixel's work, not the tile's sum (round 6): one long
-                // chain in an otherwise light tile must start with the first tiles, not in the tail
-                // (tools/timeline.py: C5 N = 8, the rank's last quarter ran a few hundred such chains)
-                atomicMax(&p.tile_cost[L.tile], cnt.segments + cnt.nodes + cnt.prims - work_at_take);
-            } else {
-                // ---- pixel finished: write back (path_tracer.cu:172-174) -----------------
-                execdiag::lanes(p.stats + 64, 11);
-                p.accum[L.pix] = make_float4(L.sum.x, L.sum.y, L.sum.z, L.passes);
-                if (AUX && p.spp > 0) {
-                    p.normal[3 * (size_t)L.pix + 0] = first_normal.x;
-                    p.normal[3 * (size_t)L.pix + 1] = first_normal.y;
-                    p.normal[3 * (size_t)L.pix + 2] = first_normal.z;
-                    p.depth[L.pix] = max_depth > 0 ? DEFAULT_RAY_TMAX : 0.f;   // a18
-                }
-                L.store_rng(p, npix);
-            }
+            // (cold fields from the kernarg segment: see the refill)
+            finish_pixel<AUX, PROBE>(kernarg_params(), L, first_normal, work_at_take, cnt, npix, max_depth);
             busy = false;
             finished = true;
         }
@@ -618,21 +615,7 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
     stamps::flush(p.stats + 16);
     pooldiag::flush(p.stats + 64);
     timeline::flush(tl);
-    if (STATS && !PROBE) {
-        uint64_t a = wave_sum(cnt.segments), b = wave_sum(cnt.nodes), c = wave_sum(cnt.prims);
-        uint64_t d = wave_sum(cnt.hits), e = wave_sum(cnt.misses);
-        const uint64_t f = wave_sum(cnt.fallbacks);   // ordered walk: certificate fallbacks
-        const uint64_t g = wave_sum(cnt.gnodes);      // wide nodes read from global memory
-        if (lane == 0) {
-            atomicAdd((unsigned long long*)&p.stats[0], (unsigned long long)a);
-            atomicAdd((unsigned long long*)&p.stats[1], (unsigned long long)b);
-            atomicAdd((unsigned long long*)&p.stats[2], (unsigned long long)c);
-            atomicAdd((unsigned long long*)&p.stats[3], (unsigned long long)d);
-            atomicAdd((unsigned long long*)&p.stats[4], (unsigned long long)e);
-            if (f) atomicAdd((unsigned long long*)&p.stats[5], (unsigned long long)f);
-            if (g) atomicAdd((unsigned long long*)&p.stats[6], (unsigned long long)g);
-        }
-    }
+    if (STATS && !PROBE) flush_walk_counters<true>(cnt, p.stats);
 }
 
 // ======================================================================================
@@ -664,10 +647,6 @@ static hipError_t launch_mk(const KParams& p, int max_workgroups, hipStream_t st
     hipLaunchKernelGGL((k_megakernel<S, A, P, T, C, H>), dim3((unsigned)grid), dim3(block), 0, stream, p);
     return hipGetLastError();
 }
-
-// The wide walk (ordered walk on a 4-wide tree) runs in the LDS kernels: the image's first
-// LDS_TREE_NODES nodes in LDS, the rest of a larger tree from global memory.
-static bool use_lds_tree(const KParams& p) { return p.ordered == 1 && p.n_wide > 0; }
 
 template <bool S, bool A, bool P, bool H>
 static hipError_t launch_mk_lds(const KParams& p, int max_workgroups, hipStream_t stream) {

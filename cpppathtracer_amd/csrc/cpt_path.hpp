@@ -166,6 +166,13 @@ __device__ __forceinline__ RayK make_rayk(const Ray& r) {
     return k;
 }
 
+// No NaN in the ray's origin or direction: trace_segment's `finite` (a ray carrying one takes the
+// reference walk with the exact ternary slab form, slab_reject<false>).
+__device__ __forceinline__ bool ray_is_finite(const Ray& ray) {
+    return !(ray.o.x != ray.o.x || ray.o.y != ray.o.y || ray.o.z != ray.o.z || ray.d.x != ray.d.x ||
+             ray.d.y != ray.d.y || ray.d.z != ray.d.z);
+}
+
 // The exact slab test's reciprocals, computed where one runs (the winner certificate and the
 // reference walk), so the ordered walk does not carry them.
 __device__ __forceinline__ RayK with_slab(const RayK& k0) {
@@ -680,6 +687,12 @@ typedef __attribute__((address_space(3))) int16_t lds_i16;
 // children (cpt_host_bvh.cpp linearise_wide), so the LDS part is the top of the tree, the part
 // every ray walks.
 // (LDS_TREE_NODES, lds_tree_nodes: cpt_internal.hpp)
+template <int BLK, int N>
+__device__ __forceinline__ void stage_wide_tree(uint4 (&s_tree)[N], const KParams& p) {
+    const uint4* src = reinterpret_cast<const uint4*>(p.nodes + wide_image_base(p));
+    for (int i = threadIdx.x; i < 7 * lds_tree_nodes(p.n_wide); i += BLK) s_tree[i] = src[i];
+    __syncthreads();
+}
 
 struct WideNode {
     f2v e[3][2], x[3][2];   // entry / exit planes per axis, children (0,1) and (2,3)
@@ -1000,7 +1013,7 @@ __device__ __forceinline__ int trace_segment(const KParams& p, const RayK& rk, b
         int n, r = -1;
         bool wide = false;
         if constexpr (LDST) {
-            if (p.ordered == 1 && p.n_wide > 0) {
+            if (use_lds_tree(p)) {
                 const int oct = (rk.d.x < 0.f ? 1 : 0) | (rk.d.y < 0.f ? 2 : 0) | (rk.d.z < 0.f ? 4 : 0);
                 r = trace_wide<STATS, BLK, HYB>(p, rsrc, oct, rk, h, code, cnt, tree, ws, suspend_at);
                 wide = true;
@@ -1185,6 +1198,44 @@ __device__ __forceinline__ uint64_t wave_sum(uint32_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
     return s;
+}
+
+// A pixel's XORWOW words in HBM: planar [6][npix].
+__device__ __forceinline__ void load_rng(const KParams& p, size_t npix, size_t pix, Xorwow& s) {
+    s.v0 = p.rng[pix];
+    s.v1 = p.rng[npix + pix];
+    s.v2 = p.rng[2 * npix + pix];
+    s.v3 = p.rng[3 * npix + pix];
+    s.v4 = p.rng[4 * npix + pix];
+    s.d = p.rng[5 * npix + pix];
+}
+__device__ __forceinline__ void store_rng(const KParams& p, size_t npix, size_t pix, const Xorwow& s) {
+    p.rng[pix] = s.v0;
+    p.rng[npix + pix] = s.v1;
+    p.rng[2 * npix + pix] = s.v2;
+    p.rng[3 * npix + pix] = s.v3;
+    p.rng[4 * npix + pix] = s.v4;
+    p.rng[5 * npix + pix] = s.d;
+}
+
+// A wave's walk counters into the STATS words: one atomic per counter by the wave's first lane
+// (fallbacks and global-node reads only when there were any).  SHADES: the kernel also shades, so
+// it counted hits and misses (the wavefront's are k_wf_shade's).
+template <bool SHADES>
+__device__ __forceinline__ void flush_walk_counters(const Counters& cnt, unsigned long long* stats) {
+    const uint64_t a = wave_sum(cnt.segments), b = wave_sum(cnt.nodes), c = wave_sum(cnt.prims);
+    const uint64_t d = SHADES ? wave_sum(cnt.hits) : 0, e = SHADES ? wave_sum(cnt.misses) : 0;
+    const uint64_t f = wave_sum(cnt.fallbacks);   // ordered walk: certificate fallbacks
+    const uint64_t g = wave_sum(cnt.gnodes);      // wide nodes read from global memory
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&stats[0], (unsigned long long)a);
+        atomicAdd(&stats[1], (unsigned long long)b);
+        atomicAdd(&stats[2], (unsigned long long)c);
+        if (SHADES) atomicAdd(&stats[3], (unsigned long long)d);
+        if (SHADES) atomicAdd(&stats[4], (unsigned long long)e);
+        if (f) atomicAdd(&stats[5], (unsigned long long)f);
+        if (g) atomicAdd(&stats[6], (unsigned long long)g);
+    }
 }
 
 }  // namespace cpt

@@ -52,9 +52,7 @@ __global__ void __launch_bounds__(query_block<LDST>()) k_ray_query(const KParams
     constexpr int BLK = query_block<LDST>();
     __shared__ uint4 s_tree[LDST ? LDS_TREE_NODES * 7 : 1];
     if (LDST) {
-        const uint4* src = reinterpret_cast<const uint4*>(p.nodes + wide_image_base(p));
-        for (int i = threadIdx.x; i < 7 * lds_tree_nodes(p.n_wide); i += BLK) s_tree[i] = src[i];
-        __syncthreads();
+        stage_wide_tree<BLK>(s_tree, p);
     }
     const uint32_t i = blockIdx.x * (uint32_t)BLK + threadIdx.x;
     size_t slot;
@@ -80,8 +78,7 @@ __global__ void __launch_bounds__(query_block<LDST>()) k_ray_query(const KParams
         ray.tmax = DEFAULT_RAY_TMAX;
     }
     const RayK rk = make_rayk(ray);
-    const bool finite = !(ray.o.x != ray.o.x || ray.o.y != ray.o.y || ray.o.z != ray.o.z || ray.d.x != ray.d.x ||
-                          ray.d.y != ray.d.y || ray.d.z != ray.d.z);
+    const bool finite = ray_is_finite(ray);
     Hit h;
     Winner win{-1, -1, DEFAULT_RAY_TMAX};
     Counters cnt{};
@@ -122,9 +119,7 @@ static hipError_t launch_query_t(const KParams& p, const int32_t* rank_obj, cons
 
 hipError_t launch_ray_query(const KParams& p, const int32_t* rank_obj, const QueryRays* rays, QueryPixels pixels,
                             const QueryOut& out, hipStream_t stream) {
-    // the wide walk runs on the LDS image, as in the megakernel (cpt_megakernel.hip use_lds_tree)
-    const bool lds = p.ordered == 1 && p.n_wide > 0;
-    return lds ? launch_query_t<true>(p, rank_obj, rays, pixels, out, stream)
+    return use_lds_tree(p) ? launch_query_t<true>(p, rank_obj, rays, pixels, out, stream)
                : launch_query_t<false>(p, rank_obj, rays, pixels, out, stream);
 }
 

@@ -42,15 +42,6 @@ __device__ __forceinline__ uint32_t wave_append(bool alive, uint32_t* counter) {
     return base + lane_rank(m);
 }
 
-__device__ __forceinline__ void load_rng(const KParams& p, size_t npix, size_t pix, Xorwow& s) {
-    s.v0 = p.rng[pix];
-    s.v1 = p.rng[npix + pix];
-    s.v2 = p.rng[2 * npix + pix];
-    s.v3 = p.rng[3 * npix + pix];
-    s.v4 = p.rng[4 * npix + pix];
-    s.d = p.rng[5 * npix + pix];
-}
-
 __device__ __forceinline__ void load_rng_slot(const WfState& w, int b, uint32_t i, Xorwow& s) {
     const uint4 a = w.rng_a[b][i];
     const uint2 c = w.rng_b[b][i];
@@ -61,15 +52,6 @@ __device__ __forceinline__ void load_rng_slot(const WfState& w, int b, uint32_t 
 __device__ __forceinline__ void store_rng_slot(const WfState& w, int b, uint32_t i, const Xorwow& s) {
     w.rng_a[b][i] = make_uint4(s.v0, s.v1, s.v2, s.v3);
     w.rng_b[b][i] = make_uint2(s.v4, s.d);
-}
-
-__device__ __forceinline__ void store_rng(const KParams& p, size_t npix, size_t pix, const Xorwow& s) {
-    p.rng[pix] = s.v0;
-    p.rng[npix + pix] = s.v1;
-    p.rng[2 * npix + pix] = s.v2;
-    p.rng[3 * npix + pix] = s.v3;
-    p.rng[4 * npix + pix] = s.v4;
-    p.rng[5 * npix + pix] = s.d;
 }
 
 // Pass start.  The first queue is the tile-ordered identity (k_wf_ident, exactly npix
@@ -120,9 +102,7 @@ __global__ void __launch_bounds__(wf_extend_block<LDST>()) k_wf_extend(const KPa
     __shared__ uint4 s_tree[LDST ? LDS_TREE_NODES * 7 : 1];
     if (LDST) {
         if ((uint32_t)blockIdx.x * BLK >= n) return;   // no ray for this block in this bounce
-        const uint4* src = reinterpret_cast<const uint4*>(p.nodes + wide_image_base(p));
-        for (int i = threadIdx.x; i < 7 * lds_tree_nodes(p.n_wide); i += BLK) s_tree[i] = src[i];
-        __syncthreads();
+        stage_wide_tree<BLK>(s_tree, p);
     }
     Counters cnt{};
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -134,8 +114,7 @@ __global__ void __launch_bounds__(wf_extend_block<LDST>()) k_wf_extend(const KPa
         ray.tmin = o.w;
         ray.tmax = DEFAULT_RAY_TMAX;
         const RayK rk = make_rayk(ray);
-        const bool finite = !(ray.o.x != ray.o.x || ray.o.y != ray.o.y || ray.o.z != ray.o.z || ray.d.x != ray.d.x ||
-                              ray.d.y != ray.d.y || ray.d.z != ray.d.z);
+        const bool finite = ray_is_finite(ray);
         Hit h;
         int code = -1;
         if (STATS) cnt.segments++;
@@ -145,18 +124,7 @@ __global__ void __launch_bounds__(wf_extend_block<LDST>()) k_wf_extend(const KPa
         w.hit_p[i] = make_float4(h.pos.x, h.pos.y, h.pos.z, __int_as_float(hit ? code : -1));
         if (hit) w.hit_n[i] = make_float4(h.normal.x, h.normal.y, h.normal.z, 0.f);
     }
-    if (STATS) {
-        const uint64_t a = wave_sum(cnt.segments), b = wave_sum(cnt.nodes), c = wave_sum(cnt.prims);
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd((unsigned long long*)&p.stats[0], (unsigned long long)a);
-            atomicAdd((unsigned long long*)&p.stats[1], (unsigned long long)b);
-            atomicAdd((unsigned long long*)&p.stats[2], (unsigned long long)c);
-        }
-        const uint64_t f = wave_sum(cnt.fallbacks);   // ordered walk: certificate fallbacks
-        if ((threadIdx.x & 63) == 0 && f) atomicAdd((unsigned long long*)&p.stats[5], (unsigned long long)f);
-        const uint64_t g = wave_sum(cnt.gnodes);      // wide nodes read from global memory
-        if ((threadIdx.x & 63) == 0 && g) atomicAdd((unsigned long long*)&p.stats[6], (unsigned long long)g);
-    }
+    if (STATS) flush_walk_counters<false>(cnt, p.stats);   // hits and misses: k_wf_shade's
 }
 
 template <bool STATS, bool AUX>
@@ -374,10 +342,7 @@ static hipError_t wf_render_any(const KParams& p, WfState& w, bool stats, bool a
 
 hipError_t launch_wavefront(const KParams& p, WfState& w, bool stats, bool aux, hipStream_t stream, int* launches) {
     if (p.width <= 0 || p.n_rows <= 0) return hipSuccess;
-    // the wide walk runs on the LDS image (+ global memory past LDS_TREE_NODES), as in the
-    // megakernel (cpt_kernels.hip use_lds_tree)
-    const bool lds = p.ordered == 1 && p.n_wide > 0;
-    return lds ? wf_render_any<true>(p, w, stats, aux, stream, launches)
+    return use_lds_tree(p) ? wf_render_any<true>(p, w, stats, aux, stream, launches)
                : wf_render_any<false>(p, w, stats, aux, stream, launches);
 }
 
