@@ -78,6 +78,7 @@ PROTOTYPES = {
     "cpt_selftest_qdiv": (_I, [_P, _I, _U64, _U64, _P, _I]),
     "cpt_set_debug_consolidation": (_I, [_P, _U32, _I, _I]),
     "cpt_set_debug_grid": (_I, [_P, _I, _I]),
+    "cpt_launch_grid_host": (_I, [_I, _I, _I, ctypes.c_int64, _I, _I, _I, _P, _P]),
     "cpt_render_adaptive": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _U32]),
     "cpt_adaptive_begin": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _U32]),
     "cpt_adaptive_step": (_I, [_P, _P]),

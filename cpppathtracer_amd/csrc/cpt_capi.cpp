@@ -132,8 +132,8 @@ int cpt_create(int device, cpt_ctx** out) {
     if (!c) return fail(nullptr, CPT_ERR_OUT_OF_MEMORY, "cpt_create: host allocation failed");
     c->device = device;
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device);
-    c->cus = std::max(c->cus, 1);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&c->grid.cus, hipDeviceAttributeMultiprocessorCount, device);
+    c->grid.cus = std::max(c->grid.cus, 1);
     if (e == hipSuccess) e = c->own_stream.create(hipStreamNonBlocking);
     for (DevEvent* ev : {&c->t_render.t0, &c->t_render.t1, &c->ev_main, &c->t_display.t0, &c->t_display.t1, &c->t_filter.t0,
                           &c->t_filter.t1, &c->t_query.t0, &c->t_query.t1})

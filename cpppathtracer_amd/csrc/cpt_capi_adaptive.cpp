@@ -32,7 +32,7 @@ int enqueue_round(cpt_ctx* c) {
         a.p.accumulate = 1;
         a.p.n_active = a.active;
     }
-    HIP_TRY(c, cpt::launch_megakernel(a.p, a.stats, a.aux, c->dbg_max_workgroups, s));
+    HIP_TRY(c, cpt::launch_megakernel(a.p, a.stats, a.aux, c->grid, s));
     cpt::AdaptiveRound r{};
     r.order = a.p.tile_order;
     r.n_active = a.active;

@@ -63,7 +63,7 @@ static int denoise_band(cpt_ctx* c, uint32_t cur_sample_idx, int y0, int y1, uin
     if (int rc = f.display.d_sink.ensure(c, cpt::DN_SINK_SLOTS)) return rc;
     HIP_TRY(c, hipEventRecord(c->t_display.t0, s));
     HIP_TRY(c, cpt::launch_denoise_mix(f.d_accum, f.d_normal, f.d_depth, f.display.d_mix, f.display.d_bgra, host_alias, f.display.d_sink, c->width,
-                                      c->height, row0, c->n_rows, y0, y1, cur_sample_idx, s));
+                                      c->height, row0, c->n_rows, y0, y1, cur_sample_idx, c->grid, s));
     HIP_TRY(c, hipEventRecord(c->t_display.t1, s));
     c->t_display.recorded = true;
     if (bgra_host && host_alias) {

@@ -111,7 +111,7 @@ int cpt_measure_read_bandwidth(cpt_ctx* c, size_t bytes, int iters, float* gbps)
     int rc;
     if ((rc = d.ensure(c, n)) != CPT_OK || (rc = o.ensure(c, 1)) != CPT_OK) return rc;
     HIP_TRY(c, hipMemsetAsync(d, 0, n * 16, c->stream()));
-    const int grid = 8 * c->cus;   // 8 blocks of 256 lanes per CU, grid-stride
+    const int grid = 8 * c->grid.cus;   // 8 blocks of 256 lanes per CU, grid-stride
     return timed_reads(c, true, iters, (double)n * 16.0, gbps,
                        [&] { return cpt::launch_stream_read(d, n, o, grid, c->stream()); });
 }
@@ -127,7 +127,7 @@ int cpt_measure_read_pattern(cpt_ctx* c, int bytes_per_lane, size_t bytes, int i
     if ((rc = d.ensure(c, n_lanes * bytes_per_lane)) != CPT_OK || (rc = o.ensure(c, 1)) != CPT_OK) return rc;
     HIP_TRY(c, hipMemsetAsync(d, 0, n_lanes * bytes_per_lane, c->stream()));
     const float* lanes = reinterpret_cast<const float*>(d.get());
-    const int grid = 8 * c->cus;
+    const int grid = 8 * c->grid.cus;
     return timed_reads(c, false, iters, (double)n_lanes * bytes_per_lane, gbps,
                        [&] { return cpt::launch_read_pattern(bytes_per_lane, lanes, n_lanes, o, grid, c->stream()); });
 }

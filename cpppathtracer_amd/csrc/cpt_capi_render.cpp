@@ -168,12 +168,13 @@ int cpt::ctx::cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStrea
     if ((rc = f.schedule.d_scratch.ensure(c, cpt::tile_schedule_scratch_bytes(c->width, c->n_rows))) != CPT_OK) return rc;
     if ((rc = f.schedule.d_cost_order.ensure(c, n_tiles(c))) != CPT_OK) return rc;
     HIP_TRY(c, cpt::launch_tile_schedule(p, passes, f.schedule.d_scratch, f.schedule.d_scratch.capacity(), f.schedule.d_cost_order,
-                                         c->dbg_max_workgroups, s));
+                                         c->grid, s));
     return CPT_OK;
 }
 
-// Tail consolidation (cpt_megakernel.hip): one slab of hand-over slots per workgroup of the
-// persistent grid (one LDS workgroup of 1024 lanes per CU), 3 x 256 chains each.  By
+// Tail consolidation (cpt_megakernel.hip): one slab of ho_slots chains per resident workgroup of
+// the consolidating kernel, by the figure its launch gets from the context's grid (one LDS
+// workgroup per CU): the slab and the grid cannot disagree (CPT_DEVERR_RESUME_CAP).  By
 // default for frames of more than 1 and at most 4 pixels per lane and chains of at least
 // 512 passes: with more pixels the tail is a small part of the render, with short chains
 // the hand-overs do not pay, and the plain kernel's tighter code wins (DESIGN.md
@@ -183,13 +184,14 @@ int cpt::ctx::cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStrea
 // this rule; profiles/r06/reh_cons_r06z.log, r06/cert/reh_c4_cons_rule.log,
 // profiles/r05/reh_cons_off_vs_auto.log).
 int cpt::ctx::consolidation_slab(cpt_ctx* c, cpt::KParams& p, int spp, uint32_t flags) {
-    const size_t cus = (size_t)c->cus;
-    const size_t frame_px = c->npix(), grid_lanes = 1024u * cus;
-    const bool cons = (flags & CPT_SCHEDULE_CONSOLIDATE) ||
-                      (!(flags & CPT_SCHEDULE_NO_CONSOLIDATE) && spp >= 512 && frame_px > grid_lanes &&
-                       frame_px <= 4u * grid_lanes);
-    if (!cons || spp <= 1) return CPT_OK;
-    const size_t cap = 3u * 256u * cus;
+    const bool forced = (flags & CPT_SCHEDULE_CONSOLIDATE) != 0;
+    if (spp <= 1 || (!forced && ((flags & CPT_SCHEDULE_NO_CONSOLIDATE) || spp < 512))) return CPT_OK;
+    long long resident = 0;
+    HIP_TRY(c, cpt::consolidating_workgroups(p, (flags & CPT_RENDER_STATS) != 0, (flags & CPT_RENDER_AUX) != 0, c->grid,
+                                             &resident));
+    const size_t frame_px = c->npix(), grid_lanes = (size_t)cpt::LDS_BLOCK * (size_t)resident;
+    if (!forced && !(frame_px > grid_lanes && frame_px <= 4u * grid_lanes)) return CPT_OK;
+    const size_t cap = cpt::consolidation_chains(resident);
     if (int rc = c->d_resume.ensure(c, cpt::HO_SLOT_QUADS * cap)) return rc;
     p.resume = c->d_resume;
     p.resume_cap = cap;
@@ -223,7 +225,7 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
         if (!p.accumulate && c->n_rows > 0) HIP_TRY(c, hipMemsetAsync(f.d_accum, 0, c->npix() * sizeof(float4), s));
         int launches = 0;
         HIP_TRY(c, hipEventRecord(c->ev_main, s));
-        HIP_TRY(c, cpt::launch_wavefront(p, f.wavefront.view, (flags & CPT_RENDER_STATS) != 0, aux, s, &launches));
+        HIP_TRY(c, cpt::launch_wavefront(p, f.wavefront.view, (flags & CPT_RENDER_STATS) != 0, aux, c->grid, s, &launches));
         c->last_launches = launches;
         HIP_TRY(c, hipEventRecord(c->t_render.t1, s));
     } else {
@@ -237,7 +239,7 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
         }
         if ((rc = consolidation_slab(c, p, spp, flags)) != CPT_OK) return rc;
         HIP_TRY(c, hipEventRecord(c->ev_main, s));
-        HIP_TRY(c, cpt::launch_megakernel(p, (flags & CPT_RENDER_STATS) != 0, aux, c->dbg_max_workgroups, s));
+        HIP_TRY(c, cpt::launch_megakernel(p, (flags & CPT_RENDER_STATS) != 0, aux, c->grid, s));
         HIP_TRY(c, hipEventRecord(c->t_render.t1, s));
         if (previous && (rc = f.schedule.previous_refresh(c, p, s)) != CPT_OK) return rc;
     }
@@ -280,8 +282,17 @@ int cpt_set_debug_consolidation(cpt_ctx* c, uint32_t flags, int keeper_spin_log2
 int cpt_set_debug_grid(cpt_ctx* c, int max_workgroups, int lanes_per_wave) {
     if (!c || max_workgroups < 0 || lanes_per_wave < 0 || lanes_per_wave > 64)
         return c ? fail(c, CPT_ERR_INVALID_ARG, "cpt_set_debug_grid: bad arguments") : CPT_ERR_INVALID_ARG;
-    c->dbg_max_workgroups = max_workgroups;
+    c->grid.max_workgroups = max_workgroups;
     c->dbg_lanes_per_wave = lanes_per_wave;
+    return CPT_OK;
+}
+
+int cpt_launch_grid_host(int cus, int blocks_per_cu, int block, int64_t tiles, int lanes, int replicate, int max_workgroups,
+                         int* workgroups, uint64_t* slab_chains) {
+    if (!workgroups || cus < 1 || blocks_per_cu < 1 || block < 1 || tiles < 0) return CPT_ERR_INVALID_ARG;
+    const long long resident = (long long)blocks_per_cu * cus;
+    *workgroups = cpt::grid_workgroups(cpt::megakernel_want(tiles, lanes, replicate, block), resident, max_workgroups);
+    if (slab_chains) *slab_chains = cpt::consolidation_chains(resident);
     return CPT_OK;
 }
 

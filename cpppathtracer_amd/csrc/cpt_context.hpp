@@ -162,7 +162,7 @@ struct TimedSpan {
 // ======================================================================================
 struct cpt_ctx {
     int device = 0;
-    int cus = 1;   // the device's compute units (read once, cpt_create)
+    cpt::LaunchGrid grid;   // the device's CUs, each kernel's blocks per CU, the test hook's cap
     // declared before the buffers and events: destroyed after them
     cpt::ctx::DevStream own_stream;
     hipStream_t user_stream = nullptr;
@@ -259,8 +259,8 @@ struct cpt_ctx {
     uint32_t dbg = 0;
     bool force_staged_gather = false;   // gather test hook (cpt_set_debug_gather)
     int keeper_spin_log2 = 0, publish_wait_log2 = 0;
-    // persistent-grid test hook (cpt_set_debug_grid): 0 = no cap, 0 = all 64 lanes
-    int dbg_max_workgroups = 0, dbg_lanes_per_wave = 0;
+    // persistent-grid test hook (cpt_set_debug_grid; its cap is grid.max_workgroups): 0 = all 64 lanes
+    int dbg_lanes_per_wave = 0;
 
     hipStream_t stream() const { return user_stream ? user_stream : (hipStream_t)own_stream; }
     size_t npix() const { return (size_t)n_rows * width; }

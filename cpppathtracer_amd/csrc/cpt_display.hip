@@ -453,22 +453,13 @@ __global__ void __launch_bounds__(DNS_LANES * DNR_WAVES, DNR_MINWAVES) k_denoise
 
 hipError_t launch_denoise_mix(const float4* accum, const float* normal, const float* depth, float* mix, uint8_t* out,
                               uint8_t* out_host, float4* sink, int width, int height, int row0, int ctx_rows, int y0, int y1,
-                              uint32_t cur_sample_idx, hipStream_t stream) {
+                              uint32_t cur_sample_idx, const LaunchGrid& grid, hipStream_t stream) {
     const int w_eff = 16 * (width / 16), h_eff = 16 * (height / 16);
     if (w_eff == 0 || h_eff == 0 || y1 <= y0) return hipSuccess;
     const float inv_idx = 1.f / float(cur_sample_idx);
-    static int cus2[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) dev = 0;
-    if (cus2[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus2[dev] = n;
-    }
     const int n_strips = (w_eff + DNS_COLS - 1) / DNS_COLS;
     const int rows = y1 - y0;
-    int per_strip = (cus2[dev] * DNR_BLOCKS_PER_CU + n_strips - 1) / n_strips;
+    int per_strip = (grid.cus * DNR_BLOCKS_PER_CU + n_strips - 1) / n_strips;
     per_strip = per_strip < 1 ? 1 : (per_strip > rows ? rows : per_strip);
     const unsigned blocks = (unsigned)(n_strips * per_strip);
     if (out_host)

@@ -4,7 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <utility>
+#include <vector>
+
 #include "cpt_device.hpp"
+#include "cpt_tuning.hpp"
 
 // Per-lane LDS stack entries of the wide walk; the host keeps the binary walk for a tree that
 // could need more (cpt_host_bvh.cpp linearise_wide).
@@ -19,6 +24,9 @@ __host__ __device__ __forceinline__ int lds_tree_nodes(int n_wide) { return n_wi
 
 // uint4s of KParams::resume per handed-over chain (k_megakernel's hand-over payload: 17 words).
 constexpr int HO_SLOT_QUADS = 5;
+// Hand-over slots per workgroup of BLK lanes: each of the waves of levels 1.. retires once and
+// hands over at most its 64 chains, so (levels - 1) x 256 slots always suffice.
+template <int BLK> constexpr int ho_slots() { return (BLK / 256 - 1) * 256; }
 
 // Camera snapshot as the kernel needs it (the reference passes the whole MotionalCamera by
 // value in PathTracerParams, path_tracer.cu:14-27; only these fields are read by RayGen).
@@ -90,19 +98,66 @@ enum : uint32_t {
     CPT_DEVERR_RESUME_CAP = 4u,        // consolidation slab too small for the grid
 };
 
+// Who sizes a persistent launch: the context's LaunchGrid, the one source of the
+// device's CU count, each kernel's blocks per CU and the test hook's cap.  Host code.
+// The arithmetic, pure (cpt_launch_grid_host runs it without a GPU).  The workgroups of `block`
+// lanes the megakernel wants for `tiles` 8x8 tiles: a lane per pixel id, a wave holding
+// lanes / replicate pixels at once (64 in normal use; fewer: DIAGNOSTIC).
+inline long long megakernel_want(long long tiles, int lanes, int replicate, int block) {
+    const int per_wave = std::max(1, lanes / std::max(1, replicate));
+    return (tiles * 64 * ((64 + per_wave - 1) / per_wave) + block - 1) / block;
+}
+// A launch that wants `want` workgroups gets every resident slot at most once, then at most
+// max_workgroups (TEST HOOK cpt_set_debug_grid; 0: no cap).  0: launch nothing.
+inline int grid_workgroups(long long want, long long resident, int max_workgroups) {
+    const long long grid = std::min(want, resident);
+    return (int)std::max(0LL, max_workgroups > 0 ? std::min<long long>(grid, max_workgroups) : grid);
+}
+// The chains of the hand-over slab (consolidation_slab): ho_slots for each resident workgroup.
+inline size_t consolidation_chains(long long resident) { return (size_t)ho_slots<LDS_BLOCK>() * (size_t)resident; }
+
+struct LaunchGrid {
+    int cus = 1;              // the device's compute units (read once, cpt_create)
+    int max_workgroups = 0;   // TEST HOOK cpt_set_debug_grid: the megakernel's cap (0: none)
+
+    // Resident workgroups of kernel `fn` at `block` lanes: its blocks per CU x the CUs.  The
+    // occupancy is asked on the kernel's first launch in this context (whose device is current:
+    // every entry point sets it) and kept; a failed query is the caller's HIP error.
+    hipError_t resident(const void* fn, int block, long long* out) {
+        auto it = std::find_if(per_cu.begin(), per_cu.end(), [fn](const auto& k) { return k.first == fn; });
+        if (it == per_cu.end()) {
+            int n = 0;
+            const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, block, 0);
+            if (e != hipSuccess) return e;
+            it = per_cu.insert(it, {fn, std::max(n, 1)});
+        }
+        *out = (long long)it->second * cus;
+        return hipSuccess;
+    }
+    // Workgroups for a launch of `fn` that wants `want`; `hooked`: the cap applies (the megakernel
+    // and its pilot; the wavefront path ignores the hook).
+    hipError_t size(const void* fn, int block, long long want, bool hooked, int* out) {
+        long long r = 0;
+        const hipError_t e = resident(fn, block, &r);
+        if (e == hipSuccess) *out = grid_workgroups(want, r, hooked ? max_workgroups : 0);
+        return e;
+    }
+
+private:
+    std::vector<std::pair<const void*, int>> per_cu;   // blocks per CU of each kernel launched so far
+};
+
 // Cost schedule (cpt_schedule.hip, DESIGN.md §Cost schedule): a `passes`-pass pilot of the
 // megakernel sums each 8x8 tile's work, then `order` (one u32 per tile) gets the tiles
 // heaviest first.  `scratch` holds tile_schedule_scratch_bytes() bytes.
 size_t tile_schedule_scratch_bytes(int width, int n_rows);
-// (max_workgroups: the persistent grid's cap, a launcher argument and not a kernel parameter;
-// 0 = none.  TEST HOOK cpt_set_debug_grid.)
-hipError_t launch_cost_pilot(const KParams& p, int max_workgroups, hipStream_t stream);   // cpt_megakernel.hip: the pilot's launch
+hipError_t launch_cost_pilot(const KParams& p, LaunchGrid& grid, hipStream_t stream);   // cpt_megakernel.hip: the pilot's launch
 // CPT_SCHEDULE_PREVIOUS: each 8x8 tile's RNG draws since `d_prev` (the Weyl plane d of the
 // states, planar [5] of p.rng), then d_prev := d; the tiles sorted heaviest first into `order`.
 hipError_t launch_tile_order_from_draws(const KParams& p, uint32_t* d_prev, void* scratch, size_t scratch_bytes,
                                         uint32_t* order, hipStream_t stream);
 hipError_t launch_tile_schedule(const KParams& p, int passes, void* scratch, size_t scratch_bytes, uint32_t* order,
-                                int max_workgroups, hipStream_t stream);
+                                LaunchGrid& grid, hipStream_t stream);
 
 // Adaptive render (cpt_adaptive.hip, DESIGN.md §Adaptive sampling).  After a round of `batch`
 // passes over the first n_active tiles of `order` (nullptr: tiles 0..n_active-1), launch_tile_noise
@@ -175,8 +230,11 @@ hipError_t launch_refit(const RefitLeaf* leaves_in, int n_leaves, const int32_t*
                         int n_levels, int n_ref, const RefitNode* nodes_plan, Box6* boxes, Node* nodes, uint32_t* image,
                         Node* leaves, hipStream_t stream);
 
-hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, int max_workgroups, hipStream_t stream);
-hipError_t launch_wavefront(const KParams& p, WfState& w, bool stats, bool aux, hipStream_t stream, int* launches);
+hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, LaunchGrid& grid, hipStream_t stream);
+// The resident workgroups of the consolidating kernel such a launch runs (consolidation_slab).
+hipError_t consolidating_workgroups(const KParams& p, bool stats, bool aux, LaunchGrid& grid, long long* out);
+hipError_t launch_wavefront(const KParams& p, WfState& w, bool stats, bool aux, LaunchGrid& grid, hipStream_t stream,
+                            int* launches);
 hipError_t wavefront_build_ident(const KParams& p, WfState& w, hipStream_t stream);
 hipError_t launch_prepare_materials(Mat* mats, const int32_t* tex_of_mat, const TexDesc* texs, int n,
                                     hipStream_t stream);
@@ -201,6 +259,6 @@ hipError_t launch_stitch_moments(const float* src, size_t src_npix, const int32_
 constexpr int DN_SINK_SLOTS = 1024 * 64;
 hipError_t launch_denoise_mix(const float4* accum, const float* normal, const float* depth, float* mix, uint8_t* out,
                               uint8_t* out_host, float4* sink, int width, int height, int row0, int ctx_rows, int y0, int y1,
-                              uint32_t cur_sample_idx, hipStream_t stream);
+                              uint32_t cur_sample_idx, const LaunchGrid& grid, hipStream_t stream);
 
 }  // namespace cpt

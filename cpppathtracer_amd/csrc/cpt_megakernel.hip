@@ -2,9 +2,10 @@
 //
 //   k_megakernel         SamplePixel (path_tracer.cu:124-175), all spp passes per launch,
 //                        per-lane path regeneration, state in registers; with what it alone
-//                        uses: Lane, decode_pixel, the coherent load/store helpers, ho_slots
+//                        uses: Lane, decode_pixel, the coherent load/store helpers
 //                        and the hand-over queue of the tail consolidation
-//   launch_mk*           the persistent grid and the STATS / AUX / PROBE / LDS / CONS / HYB ladder
+//   launch_mk*           the STATS / AUX / PROBE / LDS / CONS / HYB ladder; each launch is sized
+//                        by the context's LaunchGrid (cpt_internal.hpp)
 //   launch_megakernel    the render's entry;  launch_cost_pilot: the cost schedule's pilot
 //   timeline_read        the CPT_TIMELINE read-out (timeline::g_tl is per translation unit)
 //   k_prepare_materials  per-material constants: GetKd(0,0), emission, 1/alpha — material.cu:43-45,
@@ -64,9 +65,6 @@ __device__ __forceinline__ void st_coherent(uint32_t* a, uint32_t v) {
     __hip_atomic_store(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// Hand-over slots per workgroup: each of the waves of levels 1.. retires once and hands over
-// at most its 64 chains, so (levels - 1) x 256 slots always suffice.
-template <int BLK> constexpr int ho_slots() { return (BLK / 256 - 1) * 256; }
 
 struct Lane {
     uint32_t xy;     // x | y << 16 (frames are < 65536 pixels wide and high)
@@ -622,60 +620,56 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
 // Host-side launchers (called from cpt_capi_render.cpp and cpt_capi_adaptive.cpp).
 // ======================================================================================
 template <bool S, bool A, bool P, bool T, bool C = false, bool H = false>
-static hipError_t launch_mk(const KParams& p, int max_workgroups, hipStream_t stream) {
-    static int blocks_per_cu = -1, cus = 0;
+static hipError_t launch_mk(const KParams& p, LaunchGrid& g, hipStream_t stream) {
     constexpr int block = mk_block<T>();
-    if (blocks_per_cu < 0) {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (e == hipSuccess)
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_megakernel<S, A, P, T, C, H>, block, 0);
-        if (e != hipSuccess) return e;
-        if (blocks_per_cu < 1) blocks_per_cu = 1;
-    }
-    // persistent grid: every resident slot once; lanes pull pixels from p.work
+    // persistent grid: every resident slot once; lanes pull pixels from p.work.  (The test hook's
+    // cap makes lanes take several pixels in turn on small frames; the kernel's gridDim.x follows.)
     const long long tiles = p.n_active ? (long long)p.n_active : (long long)TileGrid{p.width, p.n_rows}.count();
-    // a wave holds p.lanes / p.replicate pixels at once (64 in normal use; fewer: DIAGNOSTIC)
-    const int per_wave = std::max(1, p.lanes / std::max(1, p.replicate));
-    long long want = (tiles * 64 * ((64 + per_wave - 1) / per_wave) + block - 1) / block;
-    long long grid = std::min<long long>(want, (long long)blocks_per_cu * cus);
-    // TEST HOOK (cpt_set_debug_grid): fewer workgroups, so that lanes take several pixels in turn
-    // on small frames; the kernel's own gridDim.x follows
-    if (max_workgroups > 0) grid = std::min<long long>(grid, max_workgroups);
-    if (grid < 1) return hipSuccess;
+    int grid = 0;
+    const hipError_t e = g.size((const void*)k_megakernel<S, A, P, T, C, H>, block,
+                                megakernel_want(tiles, p.lanes, p.replicate, block), true, &grid);
+    if (e != hipSuccess || grid < 1) return e;
     hipLaunchKernelGGL((k_megakernel<S, A, P, T, C, H>), dim3((unsigned)grid), dim3(block), 0, stream, p);
     return hipGetLastError();
 }
 
 template <bool S, bool A, bool P, bool H>
-static hipError_t launch_mk_lds(const KParams& p, int max_workgroups, hipStream_t stream) {
+static hipError_t launch_mk_lds(const KParams& p, LaunchGrid& g, hipStream_t stream) {
     if constexpr (!P && ho_slots<mk_block<true>()>() > 0) {
-        if (p.resume) return launch_mk<S, A, P, true, true, H>(p, max_workgroups, stream);   // tail consolidation
+        if (p.resume) return launch_mk<S, A, P, true, true, H>(p, g, stream);   // tail consolidation
     }
-    return launch_mk<S, A, P, true, false, H>(p, max_workgroups, stream);
+    return launch_mk<S, A, P, true, false, H>(p, g, stream);
 }
 
 template <bool S, bool A, bool P>
-static hipError_t launch_mk_any(const KParams& p, int max_workgroups, hipStream_t stream) {
-    if (!use_lds_tree(p)) return launch_mk<S, A, P, false>(p, max_workgroups, stream);
-    if (p.n_wide > LDS_TREE_NODES) return launch_mk_lds<S, A, P, true>(p, max_workgroups, stream);
-    return launch_mk_lds<S, A, P, false>(p, max_workgroups, stream);
+static hipError_t launch_mk_any(const KParams& p, LaunchGrid& g, hipStream_t stream) {
+    if (!use_lds_tree(p)) return launch_mk<S, A, P, false>(p, g, stream);
+    if (p.n_wide > LDS_TREE_NODES) return launch_mk_lds<S, A, P, true>(p, g, stream);
+    return launch_mk_lds<S, A, P, false>(p, g, stream);
 }
 
-hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, int max_workgroups, hipStream_t stream) {
+hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, LaunchGrid& g, hipStream_t stream) {
     if (p.width <= 0 || p.n_rows <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(p.work, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    if (stats && aux) return launch_mk_any<true, true, false>(p, max_workgroups, stream);
-    if (stats) return launch_mk_any<true, false, false>(p, max_workgroups, stream);
-    if (aux) return launch_mk_any<false, true, false>(p, max_workgroups, stream);
-    return launch_mk_any<false, false, false>(p, max_workgroups, stream);
+    if (stats && aux) return launch_mk_any<true, true, false>(p, g, stream);
+    if (stats) return launch_mk_any<true, false, false>(p, g, stream);
+    if (aux) return launch_mk_any<false, true, false>(p, g, stream);
+    return launch_mk_any<false, false, false>(p, g, stream);
+}
+
+// The resident workgroups of the consolidating kernel launch_mk_lds picks for these flags and
+// this tree: consolidation_slab sizes the slab by them before the launch.
+template <bool S, bool A, bool H> static const void* cons_fn() { return (const void*)k_megakernel<S, A, false, true, true, H>; }
+hipError_t consolidating_workgroups(const KParams& p, bool stats, bool aux, LaunchGrid& g, long long* out) {
+    const void* const fn[2][2][2] = {{{cons_fn<0, 0, 0>(), cons_fn<0, 0, 1>()}, {cons_fn<0, 1, 0>(), cons_fn<0, 1, 1>()}},
+                                     {{cons_fn<1, 0, 0>(), cons_fn<1, 0, 1>()}, {cons_fn<1, 1, 0>(), cons_fn<1, 1, 1>()}}};
+    return g.resident(fn[stats][aux][p.n_wide > LDS_TREE_NODES], mk_block<true>(), out);
 }
 
 // The cost schedule's pilot (cpt_schedule.hip launch_tile_schedule): the PROBE kernels.
-hipError_t launch_cost_pilot(const KParams& p, int max_workgroups, hipStream_t stream) {
-    return launch_mk_any<false, false, true>(p, max_workgroups, stream);
+hipError_t launch_cost_pilot(const KParams& p, LaunchGrid& g, hipStream_t stream) {
+    return launch_mk_any<false, false, true>(p, g, stream);
 }
 
 // DIAGNOSTIC (CPT_TIMELINE builds): copy the lane-occupancy timeline out (n words, at most

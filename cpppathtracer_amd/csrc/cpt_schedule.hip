@@ -102,7 +102,7 @@ hipError_t launch_tile_order_from_draws(const KParams& p, uint32_t* d_prev, void
 }
 
 hipError_t launch_tile_schedule(const KParams& p0, int passes, void* scratch, size_t scratch_bytes, uint32_t* order,
-                                int max_workgroups, hipStream_t stream) {
+                                LaunchGrid& grid, hipStream_t stream) {
     const int n = TileGrid{p0.width, p0.n_rows}.count();
     if (n <= 0) return hipSuccess;
     const TileScratch s = carve_tile_scratch(scratch, scratch_bytes, n);
@@ -115,7 +115,7 @@ hipError_t launch_tile_schedule(const KParams& p0, int passes, void* scratch, si
     p.tile_order = nullptr;
     p.n_active = 0;
     p.accumulate = 0;
-    e = launch_cost_pilot(p, max_workgroups, stream);
+    e = launch_cost_pilot(p, grid, stream);
     if (e != hipSuccess) return e;
     return sort_tiles_by_cost(s, n, order, stream);
 }

@@ -90,8 +90,7 @@ __global__ void __launch_bounds__(256) k_wf_raygen(const KParams p, WfState w) {
 
 // LDST: the megakernel's wide walk on the workgroup's LDS image of the tree (1024-lane blocks,
 // one per CU; the image is staged only by blocks that have rays), else the binary walks.
-constexpr int WF_LDS_BLOCK = 1024;
-template <bool LDST> constexpr int wf_extend_block() { return LDST ? WF_LDS_BLOCK : 256; }
+template <bool LDST> constexpr int wf_extend_block() { return LDST ? LDS_BLOCK : 256; }
 
 template <bool STATS, bool LDST>
 __global__ void __launch_bounds__(wf_extend_block<LDST>()) k_wf_extend(const KParams p, WfState w,
@@ -278,20 +277,6 @@ __global__ void k_wf_ident(int width, int n_rows, int32_t* q, uint32_t* count) {
 // ======================================================================================
 // Host driver: spp passes x (raygen, max_depth x (extend, shade)).
 // ======================================================================================
-static int persistent_grid(const void* fn, int block, size_t items) {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        if (cus <= 0) cus = 256;
-    }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    const long long want = (long long)((items + block - 1) / block);
-    return (int)std::max<long long>(1, std::min<long long>(want, (long long)per_cu * cus));
-}
-
 hipError_t wavefront_build_ident(const KParams& p, WfState& w, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(w.counts + 3, 0, sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
@@ -302,14 +287,14 @@ hipError_t wavefront_build_ident(const KParams& p, WfState& w, hipStream_t strea
 }
 
 template <bool S, bool A, bool T>
-static hipError_t wf_render_t(const KParams& p, WfState& w, hipStream_t stream, int* launches) {
-    const size_t npix = (size_t)p.n_rows * p.width;
+static hipError_t wf_render_t(const KParams& p, WfState& w, LaunchGrid& g, hipStream_t stream, int* launches) {
+    const long long npix = (long long)p.n_rows * p.width;   // > 0 (launch_wavefront)
     constexpr int eb = wf_extend_block<T>();
-    const int gr = persistent_grid((const void*)k_wf_raygen<A>, 256, npix);
-    const int ge = persistent_grid((const void*)k_wf_extend<S, T>, eb, npix);
-    const int gs = persistent_grid((const void*)k_wf_shade<S, A>, 256, npix);
-    hipError_t e = hipSuccess;
-    int n = 0;
+    // grid-stride kernels: a block per `block` pixels, every resident slot at most once
+    int gr = 0, ge = 0, gs = 0, n = 0;
+    hipError_t e = g.size((const void*)k_wf_raygen<A>, 256, (npix + 255) / 256, false, &gr);
+    if (e == hipSuccess) e = g.size((const void*)k_wf_extend<S, T>, eb, (npix + eb - 1) / eb, false, &ge);
+    if (e == hipSuccess) e = g.size((const void*)k_wf_shade<S, A>, 256, (npix + 255) / 256, false, &gs);
     for (int pass = 0; pass < p.spp && e == hipSuccess; ++pass) {
         hipLaunchKernelGGL(k_wf_raygen<A>, dim3(gr), dim3(256), 0, stream, p, w);
         ++n;
@@ -333,17 +318,19 @@ static hipError_t wf_render_t(const KParams& p, WfState& w, hipStream_t stream, 
 }
 
 template <bool T>
-static hipError_t wf_render_any(const KParams& p, WfState& w, bool stats, bool aux, hipStream_t stream, int* launches) {
-    if (stats && aux) return wf_render_t<true, true, T>(p, w, stream, launches);
-    if (stats) return wf_render_t<true, false, T>(p, w, stream, launches);
-    if (aux) return wf_render_t<false, true, T>(p, w, stream, launches);
-    return wf_render_t<false, false, T>(p, w, stream, launches);
+static hipError_t wf_render_any(const KParams& p, WfState& w, bool stats, bool aux, LaunchGrid& g, hipStream_t stream,
+                                int* launches) {
+    if (stats && aux) return wf_render_t<true, true, T>(p, w, g, stream, launches);
+    if (stats) return wf_render_t<true, false, T>(p, w, g, stream, launches);
+    if (aux) return wf_render_t<false, true, T>(p, w, g, stream, launches);
+    return wf_render_t<false, false, T>(p, w, g, stream, launches);
 }
 
-hipError_t launch_wavefront(const KParams& p, WfState& w, bool stats, bool aux, hipStream_t stream, int* launches) {
+hipError_t launch_wavefront(const KParams& p, WfState& w, bool stats, bool aux, LaunchGrid& g, hipStream_t stream,
+                            int* launches) {
     if (p.width <= 0 || p.n_rows <= 0) return hipSuccess;
-    return use_lds_tree(p) ? wf_render_any<true>(p, w, stats, aux, stream, launches)
-               : wf_render_any<false>(p, w, stats, aux, stream, launches);
+    return use_lds_tree(p) ? wf_render_any<true>(p, w, stats, aux, g, stream, launches)
+               : wf_render_any<false>(p, w, stats, aux, g, stream, launches);
 }
 
 }  // namespace cpt

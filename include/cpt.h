@@ -617,6 +617,14 @@ int cpt_set_debug_consolidation(cpt_ctx* ctx, uint32_t flags, int keeper_spin_lo
  * unchanged; the render is slower.  The wavefront path has no persistent grid and ignores the
  * hook.  Negative values and lanes_per_wave > 64: CPT_ERR_INVALID_ARG. */
 int cpt_set_debug_grid(cpt_ctx* ctx, int max_workgroups, int lanes_per_wave);
+/* HOST ONLY, no GPU: the arithmetic that sizes a megakernel launch, the function every launch runs
+ * with the context's own figures.  A device of `cus` compute units holding blocks_per_cu workgroups
+ * of `block` lanes of the kernel each; `tiles` 8x8 tiles to render, lanes / replicate pixels per wave
+ * (64, 1 in normal use); max_workgroups as in cpt_set_debug_grid.  workgroups: the launch's grid
+ * (0: nothing is launched).  slab_chains (may be NULL): the chains the tail consolidation's
+ * hand-over slab holds for that device, a workgroup's slots for each resident workgroup. */
+int cpt_launch_grid_host(int cus, int blocks_per_cu, int block, int64_t tiles, int lanes, int replicate, int max_workgroups,
+                         int* workgroups, uint64_t* slab_chains);
 
 #ifdef __cplusplus
 }  /* extern "C" */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compare the kernels of the ray units' device code between a commit and the working tree, kernel
+"""Compare the kernels of the UNITS' device code between a commit and the working tree, kernel
 by kernel: the instruction stream with its local label numbers normalised, and the register, spill,
 scratch and LDS figures of the code object's metadata.
 
@@ -21,7 +21,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from cpppathtracer_amd import build as _build   # noqa: E402
 
-UNITS = ["cpt_megakernel", "cpt_wavefront", "cpt_query"]
+UNITS = ["cpt_megakernel", "cpt_wavefront", "cpt_query", "cpt_display", "cpt_schedule"]
 FLAGS = [f for f in _build.HIPCC_FLAGS if f != "-shared"] + ["--cuda-device-only", "-S"]
 META = [".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
         ".group_segment_fixed_size"]
