@@ -97,6 +97,10 @@ PROTOTYPES = {
     "cpt_trace_rays": (_I, [_P, _SZ, _P, _P, _P, _U32, _P, _P, _P]),
     "cpt_pick": (_I, [_P, _P, _I, _I, _U32, _P, _P]),
     "cpt_last_query_ms": (_I, [_P, _P]),
+    "cpt_reproject_accum": (_I, [_P, _P, _P, _I, ctypes.c_float, _U32]),
+    "cpt_last_reproject_ms": (_I, [_P, _P]),
+    "cpt_last_reproject_launch_ms": (_I, [_P, _P]),
+    "cpt_reproject_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_float, _P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1

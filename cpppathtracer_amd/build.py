@@ -22,6 +22,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_kernels.hip"),
     os.path.join(CSRC, "cpt_wavefront.hip"),
     os.path.join(CSRC, "cpt_query.hip"),
+    os.path.join(CSRC, "cpt_reproject.hip"),
     os.path.join(CSRC, "cpt_capi.cpp"),
     os.path.join(CSRC, "cpt_capi_render.cpp"),
     os.path.join(CSRC, "cpt_capi_gather.cpp"),
@@ -30,6 +31,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_capi_adaptive.cpp"),
     os.path.join(CSRC, "cpt_capi_filter.cpp"),
     os.path.join(CSRC, "cpt_capi_query.cpp"),
+    os.path.join(CSRC, "cpt_capi_reproject.cpp"),
     os.path.join(CSRC, "cpt_scene.cpp"),
     os.path.join(CSRC, "cpt_host_bvh.cpp"),
     os.path.join(CSRC, "cpt_host_rng.cpp"),

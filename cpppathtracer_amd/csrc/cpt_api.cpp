@@ -833,6 +833,27 @@ bool PathTracer::ReadGBuffer(std::vector<int32_t>& id, std::vector<float>& t, st
     return true;
 }
 
+bool PathTracer::Reproject(const MotionalCamera& from, int max_history, float plane_tol) {
+    if (!camera_) {
+        err_ = "Reproject: SetCamera first";
+        return false;
+    }
+    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
+    const MotionalCamera to = query_camera(*camera_), old = query_camera(from);
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!SyncScene() || !EnsureFrame(to)) return false;
+    if (frame_) {
+        err_ = "Reproject: not available with SetDevices(n > 1), the row tiles own their accumulators";
+        return false;
+    }
+    cpt_ctx* ctx = tiles_[0].ctx;
+    if (cpt_reproject_accum(ctx, reinterpret_cast<const cpt_camera*>(&old), reinterpret_cast<const cpt_camera*>(&to), max_history,
+                            plane_tol, ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK ||
+        cpt_synchronize(ctx) != CPT_OK)
+        return Fail("cpt_reproject_accum", ctx);
+    return true;
+}
+
 // Counters summed over the tiles (the render flags do not ask for CPT_RENDER_STATS, so these
 // are the counters of the last counting render; GetStats after cpt-level counting renders).
 bool PathTracer::GetStats(cpt_stats* out) {

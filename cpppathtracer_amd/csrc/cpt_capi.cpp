@@ -136,7 +136,8 @@ int cpt_create(int device, cpt_ctx** out) {
     c->grid.cus = std::max(c->grid.cus, 1);
     if (e == hipSuccess) e = c->own_stream.create(hipStreamNonBlocking);
     for (DevEvent* ev : {&c->t_render.t0, &c->t_render.t1, &c->ev_main, &c->t_display.t0, &c->t_display.t1, &c->t_filter.t0,
-                          &c->t_filter.t1, &c->t_query.t0, &c->t_query.t1})
+                          &c->t_filter.t1, &c->t_query.t0, &c->t_query.t1, &c->t_reproject.t0, &c->t_reproject.t1,
+                          &c->ev_reproject[0], &c->ev_reproject[1]})
         if (e == hipSuccess) e = ev->create();
     for (DevEvent* ev : {&c->ev_ready, &c->ev_gathered, &c->ev_caller, &c->ev_copied, &c->ev_round, &c->ev_switch})
         if (e == hipSuccess) e = ev->create(hipEventDisableTiming);

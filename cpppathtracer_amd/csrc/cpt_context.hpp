@@ -3,6 +3,7 @@
 // cpt_capi_render.cpp (render launches, tile schedules, timing), cpt_capi_adaptive.cpp (adaptive
 // render), cpt_capi_filter.cpp (a-trous filter), cpt_capi_gather.cpp (row-tile gather),
 // cpt_capi_display.cpp (display path), cpt_capi_query.cpp (G-buffer, ray queries, picking),
+// cpt_capi_reproject.cpp (reprojection to a moved camera),
 // cpt_capi_probes.cpp (diagnostic probes, self-tests) and
 // cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  Host code only.
 #pragma once
@@ -135,6 +136,13 @@ struct GBufferState {
     bool valid = false;                 // a cpt_gbuffer has been queued since cpt_set_frame
 };
 
+// The reprojection (cpt_capi_reproject.cpp; allocated on the frame's first cpt_reproject_accum).
+struct ReprojectState {
+    DevBuf<int32_t> d_id;      // the G-buffer at the camera the history was rendered with: object
+    DevBuf<float> d_t;         // index and hit distance per pixel
+    DevBuf<float4> d_accum;    // the plane the next call writes; swapped with Frame::d_accum behind it
+};
+
 struct Frame {
     bool set = false, rng_set = false;
     DevBuf<int32_t> d_rows;
@@ -149,6 +157,7 @@ struct Frame {
     AdaptiveState adaptive;
     FilterState filter;
     GBufferState gbuffer;
+    ReprojectState reproject;
 };
 
 // A pair of timing events around a subsystem's last launches, once they have been recorded.
@@ -171,6 +180,8 @@ struct cpt_ctx {
     TimedSpan t_display;   // the last display kernel (k_denoise_rows)
     TimedSpan t_filter;    // the last cpt_filter_frame's launches
     TimedSpan t_query;     // the last query kernel (cpt_gbuffer, cpt_trace_rays, cpt_pick)
+    TimedSpan t_reproject; // the last cpt_reproject_accum's launches ...
+    DevEvent ev_reproject[2];   // ... and the two points between them: after each G-buffer trace
     std::string err;
 
     // scene

@@ -14,27 +14,6 @@
 
 namespace cpt {
 
-// MotionalCamera::RayGen (motional_camera.cu:202-213) with the lens sample taken as zero: ray_gen
-// (cpt_path.hpp) operation for operation with rd = 0, so it is the ray the integrator shoots when
-// lens_radius == 0 (u * 0 + v * 0 keeps its zeros' signs), without the three draws.
-__device__ __forceinline__ Ray ray_gen_centre(const CamK& c, int x, int y) {
-    const v3 rd = mk1(0.f);
-    v3 u = mk(c.u[0], c.u[1], c.u[2]), v = mk(c.v[0], c.v[1], c.v[2]);
-    v3 origin = mk(c.origin[0], c.origin[1], c.origin[2]);
-    v3 offset = u * rd.x + v * rd.y;
-    float dx = x > 0 ? qdiv_raw(float(x), c.inv_w) : 0.f;
-    float dy = y > 0 ? qdiv_raw(float(y), c.inv_h) : 0.f;
-    Ray ray;
-    ray.o = origin + offset;
-    v3 tl = mk(c.top_left[0], c.top_left[1], c.top_left[2]);
-    v3 hz = mk(c.horizontal[0], c.horizontal[1], c.horizontal[2]);
-    v3 vt = mk(c.vertical[0], c.vertical[1], c.vertical[2]);
-    ray.d = normalize((((tl + dx * hz) + dy * vt) - origin) - offset);
-    ray.tmin = 0.f;
-    ray.tmax = DEFAULT_RAY_TMAX;
-    return ray;
-}
-
 // LDST: the wide walk on the workgroup's LDS image of the tree, in the megakernel's LDS block shape
 // (LDS_BLOCK lanes, one workgroup per CU: the image and the 16-bit walk stacks, CPT_WSTACK entries
 // per lane, take 120 KB of the CU's 160 KB); else WIDE_LANES blocks and the binary walks.

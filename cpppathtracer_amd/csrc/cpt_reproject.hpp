@@ -1,0 +1,192 @@
+// cpt_reproject.hpp — reprojection of the accumulated frame to a moved camera,
+// shared by the device (cpt_reproject.hip) and the host (cpt_reproject_host).
+//
+// Backward reprojection: the new pixel's first hit (or, for the sky, its direction as a point at
+// infinity) is projected into the camera the history was rendered with, and the four accumulator
+// pixels around that position are blended bilinearly, each only if it saw the same object on the
+// new hit's tangent plane.  Means and pass counts are blended apart, so the result is again
+// (rgb sum, integer pass count), which every consumer of the accumulator reads.
+//
+// f32 `+ - * /`, comparisons and floorf only, each expression rounded as written (no contraction,
+// no transcendental, no sqrt; `/` is the correctly rounded operation of the build, DESIGN.md
+// §Numerics), so the device, the host entry and the numpy restatement in tests/reproject_model.py
+// agree bit for bit.  The reference has no counterpart: MotionalCamera::Refresh restarts Mix at
+// 1 / 1 when the camera moves (motional_camera.cu, path_tracer.cu:177-254).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/cpt.h"
+#include "cpt_internal.hpp"
+
+namespace cpt {
+namespace reproject {
+
+constexpr float SNAP = 0.03125f;         // 1/32: a position this close to a pixel is that pixel
+constexpr float MIN_WEIGHT = 0.015625f;  // 1/64: less valid bilinear weight than this is no history
+
+struct V3 { float x, y, z; };
+struct Px { float r, g, b, n; };   // an accumulator pixel: rgb sums and the pass count
+
+__host__ __device__ inline bool finite(float x) {
+#pragma clang fp contract(off)
+    return x - x == 0.0f;   // inf - inf and NaN - NaN are NaN
+}
+
+__host__ __device__ inline float dot(const V3& a, const V3& b) {
+#pragma clang fp contract(off)
+    return (a.x * b.x + a.y * b.y) + a.z * b.z;
+}
+
+__host__ __device__ inline V3 sub(const V3& a, const V3& b) {
+#pragma clang fp contract(off)
+    return V3{a.x - b.x, a.y - b.y, a.z - b.z};
+}
+
+// o + t * d, the point of a G-buffer ray at distance t
+__host__ __device__ inline V3 at(const V3& o, float t, const V3& d) {
+#pragma clang fp contract(off)
+    return V3{o.x + t * d.x, o.y + t * d.y, o.z + t * d.z};
+}
+
+// What the projection into the old camera reads of it, from its GetCopy outputs alone:
+// T = top_left_corner - origin, Hh = horizontal, Vv = vertical, w, and the five dot products that
+// do not depend on the pixel.  Formed once per call, on the host, for the device and the host entry.
+struct OldView {
+    V3 o, T, Hh, Vv, w;
+    float Tw, TH, HH, TV, VV;
+    float fw, fh;   // the frame's size
+};
+
+inline V3 v3_of(const cpt_float3& a) { return V3{a.x, a.y, a.z}; }
+
+inline OldView old_view(const cpt_camera& c) {
+#pragma clang fp contract(off)
+    OldView v;
+    v.o = v3_of(c.origin);
+    v.T = sub(v3_of(c.top_left_corner), v.o);
+    v.Hh = v3_of(c.horizontal);
+    v.Vv = v3_of(c.vertical);
+    v.w = v3_of(c.w);
+    v.Tw = dot(v.T, v.w);
+    v.TH = dot(v.T, v.Hh);
+    v.HH = dot(v.Hh, v.Hh);
+    v.TV = dot(v.T, v.Vv);
+    v.VV = dot(v.Vv, v.Vv);
+    v.fw = (float)c.width;
+    v.fh = (float)c.height;
+    return v;
+}
+
+// The old frame's position (fx, fy), in pixels, of q: a point relative to the old camera's origin,
+// or a direction (a point at infinity).  RayGen samples pixel x at dx = x / W, with no centre
+// offset, so pixel x sits at fx = x.  false: behind or beside the old camera, or not finite.
+__host__ __device__ inline bool project(const OldView& v, const V3& q, float& fx, float& fy) {
+#pragma clang fp contract(off)
+    const float qw = dot(q, v.w);
+    if (!(qw < 0.0f) || !finite(qw)) return false;
+    const float s = v.Tw / qw;
+    const float dx = (s * dot(q, v.Hh) - v.TH) / v.HH;
+    const float dy = (s * dot(q, v.Vv) - v.TV) / v.VV;
+    fx = dx * v.fw;
+    fy = dy * v.fh;
+    return finite(fx) && finite(fy);
+}
+
+// A position within SNAP of a pixel becomes that pixel (floorf(f + 0.5f) is rint(f) wherever the
+// two can differ by at most SNAP from f).
+__host__ __device__ inline float snap(float f) {
+#pragma clang fp contract(off)
+    const float r = floorf(f + 0.5f);
+    float d = f - r;
+    if (d < 0.0f) d = -d;
+    return d <= SNAP ? r : f;
+}
+
+// One output pixel.  `src` gives the old frame: src.accum(k), src.id0(k), src.t0(k) and
+// src.dir0(x, y, k) of a pixel k = y * width + x inside it.  id1, t1, n1 and d1 are the new
+// pixel's G-buffer entry and centre-ray direction, o1 the new camera's origin.
+template <typename Src>
+__host__ __device__ inline Px pixel(const Src& src, const OldView& v, const V3& o1, int width, int height, int32_t id1,
+                                    float t1, const V3& n1, const V3& d1, float max_history, float plane_tol) {
+#pragma clang fp contract(off)
+    const Px none{0.0f, 0.0f, 0.0f, 0.0f};
+    const bool hit = id1 >= 0;
+    const V3 P = at(o1, t1, d1);
+    const V3 q = hit ? sub(P, v.o) : d1;
+    float fx, fy;
+    if (!project(v, q, fx, fy)) return none;
+    fx = snap(fx);
+    fy = snap(fy);
+    // the taps x0, x0 + 1 (y0, y0 + 1) reach the frame only from here; also keeps the int casts defined
+    if (!(fx > -1.0f && fx < v.fw && fy > -1.0f && fy < v.fh)) return none;
+    const float flx = floorf(fx), fly = floorf(fy);
+    const int x0 = (int)flx, y0 = (int)fly;
+    const float wx = fx - flx, wy = fy - fly;
+    const float bound = plane_tol * t1;
+    float Wt = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f;
+    for (int b = 0; b < 2; ++b)
+        for (int a = 0; a < 2; ++a) {
+            const int x = x0 + a, y = y0 + b;
+            if (x < 0 || x >= width || y < 0 || y >= height) continue;
+            const size_t k = (size_t)y * width + x;
+            if (src.id0(k) != id1) continue;
+            const Px A = src.accum(k);
+            if (!(A.n >= 1.0f) || !finite(A.r) || !finite(A.g) || !finite(A.b)) continue;
+            if (hit) {
+                // the tap's own hit point lies on the new hit's tangent plane
+                float pd = dot(sub(at(v.o, src.t0(k), src.dir0(x, y, k)), P), n1);
+                if (pd < 0.0f) pd = -pd;
+                if (!(pd <= bound)) continue;
+            }
+            const float wgt = (a ? wx : 1.0f - wx) * (b ? wy : 1.0f - wy);
+            // the one tap of weight 1, within the cap: its float4 as it is
+            if (wgt == 1.0f && A.n <= max_history) return A;
+            Wt += wgt;
+            sr += wgt * (A.r / A.n);
+            sg += wgt * (A.g / A.n);
+            sb += wgt * (A.b / A.n);
+            sn += wgt * A.n;
+        }
+    if (!(Wt >= MIN_WEIGHT)) return none;
+    const float n = sn / Wt;
+    const float cap = floorf(n < max_history ? n : max_history);
+    if (!(cap >= 1.0f)) return none;
+    return Px{(sr / Wt) * cap, (sg / Wt) * cap, (sb / Wt) * cap, cap};
+}
+
+// The old frame as plain arrays (the host entry).
+struct PlaneSrc {
+    const Px* in;
+    const int32_t* id;
+    const float* t;
+    const float* dir3;
+    __host__ __device__ Px accum(size_t k) const { return in[k]; }
+    __host__ __device__ int32_t id0(size_t k) const { return id[k]; }
+    __host__ __device__ float t0(size_t k) const { return t[k]; }
+    __host__ __device__ V3 dir0(int, int, size_t k) const { return V3{dir3[3 * k], dir3[3 * k + 1], dir3[3 * k + 2]}; }
+};
+
+}  // namespace reproject
+
+// k_reproject_accum's arguments (cpt_reproject.hip): both cameras as ray_gen_centre reads them, the
+// old one as the projection reads it, the G-buffer planes of a width x height full frame (id0, t0
+// at the old camera; id1, t1, normal1 at the new one), the accumulator and the plane the result
+// goes to (not the same).
+struct ReprojectArgs {
+    CamK cam0, cam1;
+    reproject::OldView view0;
+    int width, height;
+    const int32_t* id0;
+    const float* t0;
+    const int32_t* id1;
+    const float* t1;
+    const float* normal1;
+    const float4* in;
+    float4* out;
+    float max_history, plane_tol;
+};
+hipError_t launch_reproject(const ReprojectArgs& a, hipStream_t stream);
+
+}  // namespace cpt

@@ -38,6 +38,25 @@ def camera_get_copy(cam):
     return c
 
 
+def reproject_host(cam0, cam1, dir0, dir1, id0, t0, id1, t1, normal1, accum, max_history=32, plane_tol=1e-2):
+    """cpt_reproject_host (no GPU): the function reproject_accum's kernel runs, on host arrays.  cam0 /
+    cam1 after camera_get_copy; dir0 / dir1 [npix, 3] their centre-ray directions; (id0, t0) and
+    (id1, t1, normal1) the G-buffers at cam0 and cam1; accum [npix, 4].  Returns the new [npix, 4]."""
+    L = _lib.load()
+    a = np.ascontiguousarray(np.array(cam0, dtype=CAMERA_DTYPE))
+    b = np.ascontiguousarray(np.array(cam1, dtype=CAMERA_DTYPE))
+    W, H = int(a["width"].reshape(-1)[0]), int(a["height"].reshape(-1)[0])
+    n = W * H
+    f32 = lambda v, shape: np.ascontiguousarray(v, dtype=np.float32).reshape(shape)
+    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32).reshape(n)
+    d0, d1, nn, acc = f32(dir0, (n, 3)), f32(dir1, (n, 3)), f32(normal1, (n, 3)), f32(accum, (n, 4))
+    i0, i1, tt0, tt1 = i32(id0), i32(id1), f32(t0, n), f32(t1, n)
+    out = np.zeros((n, 4), dtype=np.float32)
+    check(L.cpt_reproject_host(_p(a), _p(b), W, H, _p(d0), _p(d1), _p(i0), _p(tt0), _p(i1), _p(tt1), _p(nn), _p(acc),
+                               int(max_history), ctypes.c_float(plane_tol), _p(out)))
+    return out
+
+
 class Renderer:
     def __init__(self, device: int = 0):
         self._L = _lib.load()
@@ -309,6 +328,31 @@ class Renderer:
         """Device time of the last gbuffer, trace_rays or pick kernel (HIP events); waits for it."""
         ms = ctypes.c_float(0)
         self._check(self._L.cpt_last_query_ms(self._ctx, ctypes.byref(ms)))
+        return float(ms.value)
+
+    # -- reprojection ----------------------------------------------------------------
+    def reproject_accum(self, cam_from, cam_to, max_history=32, plane_tol=1e-2, flags=0):
+        """cpt_reproject_accum: the accumulator, rendered with cam_from, looked up at cam_to (both
+        after camera_get_copy): each new pixel's first hit is projected into the old frame and the
+        four pixels around it blended, a tap only where it saw the same object on the new hit's
+        tangent plane (within plane_tol x the hit distance); pass counts are capped at
+        max_history, pixels without history end as zeros.  Needs a full frame and a static scene;
+        leaves cam_to's G-buffer in read_gbuffer and drops the frame's adaptive result.
+        flags: CPT_TRAVERSAL_* bits only.  Asynchronous."""
+        a = np.ascontiguousarray(np.array(cam_from, dtype=CAMERA_DTYPE))
+        b = np.ascontiguousarray(np.array(cam_to, dtype=CAMERA_DTYPE))
+        self._check(self._L.cpt_reproject_accum(self._ctx, _p(a), _p(b), int(max_history), ctypes.c_float(plane_tol),
+                                                int(flags)))
+
+    def last_reproject_ms(self, split=False):
+        """Device time of the last reproject_accum, all its launches (HIP events); waits for it.
+        split: (trace at cam_from, trace at cam_to, look-up kernel) instead of their total."""
+        if split:
+            ms3 = (ctypes.c_float * 3)()
+            self._check(self._L.cpt_last_reproject_launch_ms(self._ctx, ms3))
+            return tuple(float(v) for v in ms3)
+        ms = ctypes.c_float(0)
+        self._check(self._L.cpt_last_reproject_ms(self._ctx, ctypes.byref(ms)))
         return float(ms.value)
 
     def tile_costs(self, cam, passes, max_depth, ordered=True):

@@ -4,7 +4,12 @@
 //   cpt_headless [--scene s3|s4|s1000] [--width W] [--height H] [--spp N] [--depth D] [--seed S]
 //                [--out radiance.bin] [--dispatch K --bgra frame.bin] [--pfm image.pfm]
 //                [--texture file.ppm|file.cptex] [--dump-scene objects.bin] [--devices N]
-//                [--objects N] [--animate K] [--pick X,Y]
+//                [--objects N] [--animate K] [--pick X,Y] [--orbit N [--reproject]]
+//
+// --orbit N renders N frames of --spp passes each into one accumulator while the camera turns about
+// the vertical axis through its look-at point, one degree per frame.  Without --reproject the
+// frames are simply added (the image smears); with it PathTracer::Reproject carries the history to
+// each new camera first.  --out / --pfm then hold the last frame.
 //
 // --pick X,Y prints the object (AddObject index, -1 = sky) under pixel (X, Y) of the image and its
 // distance (PathTracer::Pick: one centre ray, no render), then exits.
@@ -159,12 +164,19 @@ int main(int argc, char** argv) {
     // --filter [LEVELS] (with --adaptive): the variance-guided a-trous filter of the adaptive frame
     // (PathTracer::FilterRadiance, 5 levels by default); --pfm then gets the filtered image
     int filter_levels = -1;
+    int orbit = 0;
+    bool reproject = false;
     for (int i = 1; i < argc; i += 2) {
         std::string k = argv[i];
         if (k == "--filter") {
             const bool has_value = i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0;
             filter_levels = has_value ? std::stoi(argv[i + 1]) : 5;
             if (!has_value) --i;
+            continue;
+        }
+        if (k == "--reproject") {
+            reproject = true;
+            --i;
             continue;
         }
         if (i + 1 >= argc) break;
@@ -185,6 +197,7 @@ int main(int argc, char** argv) {
         else if (k == "--objects") n_objects = std::stoi(v);
         else if (k == "--animate") animate = std::stoi(v);
         else if (k == "--pick") pick = v;
+        else if (k == "--orbit") orbit = std::stoi(v);
         else if (k == "--adaptive") adaptive = std::stof(v);
         else if (k == "--min-spp") min_spp = std::stoi(v);
         else if (k == "--batch") batch = std::stoi(v);
@@ -291,6 +304,22 @@ int main(int argc, char** argv) {
             if (!tracer.FilterRadiance(filter_levels)) { fprintf(stderr, "FilterRadiance: %s\n", tracer.LastError().c_str()); return 1; }
             printf("filtered: %d levels\n", filter_levels);
         }
+    } else if (orbit > 0) {
+        // one degree per frame about the vertical axis through the look-at point, in f32 as written
+        const float c = 0.99984770f, s = 0.01745241f;
+        float dx = cam->origin_.x - cam->look_at_.x, dz = cam->origin_.z - cam->look_at_.z;
+        for (int f = 0; f < orbit; ++f) {
+            const MotionalCamera from = *cam;   // the camera the accumulator was rendered with
+            if (f > 0) {
+                const float nx = c * dx + s * dz, nz = c * dz - s * dx;
+                dx = nx;
+                dz = nz;
+                cam->SetOrigin(cam->look_at_.x + dx, cam->origin_.y, cam->look_at_.z + dz);
+                if (reproject && !tracer.Reproject(from)) { fprintf(stderr, "Reproject: %s\n", tracer.LastError().c_str()); return 1; }
+            }
+            if (!tracer.Render(spp, f > 0)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
+        }
+        printf("orbit: %d frames of %d spp%s\n", orbit, spp, reproject ? ", reprojected" : "");
     } else if (!tracer.Render(spp, false)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
     for (int f = 1; f <= animate; ++f) {
         const auto t0 = std::chrono::steady_clock::now();

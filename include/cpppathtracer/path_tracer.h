@@ -12,7 +12,7 @@
 //   SetMaxRecursionDepth, SetSeed, SetDevice, SetDevices (row tiling over several GPUs),
 //   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance,
 //   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
-//   GetStats, Stop.
+//   Reproject, GetStats, Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -102,6 +102,17 @@ public:
     // index (-1: sky), hit distance, normal and albedo (float[width*height*3] each) per pixel.
     bool ReadGBuffer(std::vector<int32_t>& id, std::vector<float>& t, std::vector<float>& normal3,
                      std::vector<float>& albedo3);
+    // Keeps the accumulated radiance through a camera move (cpt_reproject_accum): the accumulator,
+    // rendered with `from` (a copy of the camera object the caller kept from its last Render), is
+    // looked up at the current camera, so the next Render(spp, true) adds to the history instead
+    // of restarting it.  A pixel keeps at most max_history passes; a history pixel counts only
+    // where it saw the same object within plane_tol x the hit distance of the new hit's tangent
+    // plane; pixels without history restart.  Static scene only (after UpdateObject, restart with
+    // Render(spp, false)); mirrors and glass lag until new passes outweigh the history.  The
+    // current camera's sample index, the RNG and the display state are left as they are; the
+    // DispatchRay loop (the Mix running mean with its one global sample index) does not use it.
+    // Not available with SetDevices(n > 1): the row tiles own their accumulators (false, LastError).
+    bool Reproject(const MotionalCamera& from, int max_history = 32, float plane_tol = 1e-2f);
     bool GetStats(cpt_stats* out);
     void Stop();                                 // stop the render thread (also in ~PathTracer)
     const std::string& LastError() const { return err_; }

@@ -399,7 +399,8 @@ int cpt_filter_level_host(int width, int height, int step, const float* in_rgbv,
  * frame, allocated at the first call and dropped by cpt_set_frame.  Asynchronous, on the context's
  * stream; CPT_ERR_STATE while an adaptive render is pending. */
 int cpt_gbuffer(cpt_ctx* ctx, const cpt_camera* cam, uint32_t flags);
-/* The last cpt_gbuffer's result (CPT_ERR_STATE if none since cpt_set_frame): id [n_rows*width], t
+/* The last cpt_gbuffer's result, or the G-buffer at `to` of a later cpt_reproject_accum
+ * (CPT_ERR_STATE if neither since cpt_set_frame): id [n_rows*width], t
  * [n_rows*width], normal3 and albedo3 [n_rows*width][3]; any may be NULL.  capacity_pixels below
  * n_rows*width: CPT_ERR_INVALID_ARG, nothing written.  Waits. */
 int cpt_read_gbuffer(cpt_ctx* ctx, int32_t* id, float* t, float* normal3, float* albedo3, size_t capacity_pixels);
@@ -416,6 +417,53 @@ int cpt_pick(cpt_ctx* ctx, const cpt_camera* cam, int x, int y, uint32_t flags, 
 /* Device time of the last cpt_gbuffer, cpt_trace_rays or cpt_pick kernel (HIP events on the
  * context's stream); waits for it. */
 int cpt_last_query_ms(cpt_ctx* ctx, float* ms);
+/* Reprojection of the accumulated frame to a moved camera (an addition: the reference throws the
+ * history away when the camera moves, MotionalCamera::Refresh and Mix restarting at 1 / 1;
+ * DESIGN.md §21).  `from` is the camera the accumulator was rendered with, `to` the new one, both
+ * after cpt_camera_get_copy and of the frame's size.  For every pixel of `to` the call looks up its
+ * first hit (for the sky: its direction, a point at infinity, so the sky follows rotations only) in
+ * the frame as `from` saw it, blends the four accumulator pixels around that position bilinearly
+ * (positions within 1/32 of a pixel snap to it) and keeps a tap only if it holds at least one pass
+ * and finite rgb, saw the same object, and its own hit point lies within plane_tol x the new hit's
+ * distance of the new hit's tangent plane.  The means and the pass counts are blended apart: a
+ * pixel ends as (mean x n, n) with n = floor(min(blended count, max_history)), an integer as every
+ * consumer of the accumulator expects, or as (0, 0, 0, 0) where less than 1/64 of the bilinear
+ * weight was valid (disocclusions, the frame's new border): the next CPT_RENDER_ACCUMULATE render
+ * starts those pixels afresh.  A pixel that maps exactly onto a valid old pixel of at most
+ * max_history passes keeps that pixel's four floats unchanged, so from == to leaves such an
+ * accumulator bit for bit as it was.
+ * The call traces the G-buffer at `from` into history planes of its own and the G-buffer at `to`
+ * into the frame's ordinary G-buffer (cpt_read_gbuffer afterwards returns `to`'s), both by
+ * the walk of `flags` (CPT_TRAVERSAL_* bits only), then runs the look-up into a second plane that
+ * becomes the accumulator.  It writes the accumulator and the G-buffer and nothing else of the
+ * render state (RNG states, aux buffers, display state and filter planes stay), and drops the
+ * frame's adaptive result, whose moments no longer describe the accumulator: cpt_read_noise,
+ * cpt_read_moments and cpt_filter_frame return CPT_ERR_STATE until the next adaptive render or
+ * cpt_write_moments.  Asynchronous, on the context's stream, ordered like every other call; its
+ * planes are allocated at the first call and dropped by cpt_set_frame.
+ * CPT_ERR_STATE: no scene, no frame, a frame that is not full (rows == NULL, as cpt_filter_frame;
+ * a row-tiled render reprojects on the context its tiles were gathered into), an adaptive render
+ * pending.  CPT_ERR_INVALID_ARG: a NULL camera, a camera of another size, max_history < 1, a
+ * plane_tol that is negative or not finite, a flag bit outside CPT_TRAVERSAL_*.  Nothing is written
+ * on an error.
+ * Limits.  Static scene: both traces walk the current scene, so after cpt_update_objects the caller
+ * clears the accumulator or accepts stale history on the moved objects.  Outgoing radiance is
+ * reused as if it did not depend on the view: mirrors and glass lag until new passes outweigh
+ * max_history.  The wrappers' defaults are max_history 32 and plane_tol 1e-2. */
+int cpt_reproject_accum(cpt_ctx* ctx, const cpt_camera* from, const cpt_camera* to, int max_history, float plane_tol,
+                        uint32_t flags);
+/* Device time of the last cpt_reproject_accum, all its launches (HIP events on the context's
+ * stream); waits for it.  cpt_last_reproject_launch_ms: the same split into ms3[0..2], the trace
+ * at `from`, the trace at `to` and the look-up kernel. */
+int cpt_last_reproject_ms(cpt_ctx* ctx, float* ms);
+int cpt_last_reproject_launch_ms(cpt_ctx* ctx, float* ms3);
+/* HOST ONLY, no GPU: the function the device runs, on a width x height frame.  cam0 / cam1: the
+ * old and the new camera (after cpt_camera_get_copy, of that size); dir0 / dir1 [npix][3] their
+ * centre-ray directions (the G-buffer's rays); id0, t0 the G-buffer at cam0 and id1, t1, normal1
+ * the G-buffer at cam1; accum_in / accum_out [npix][4] (not the same array). */
+int cpt_reproject_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0,
+                       const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
+                       const float* normal1, const float* accum_in, int max_history, float plane_tol, float* accum_out);
 /* Device-to-device copy of the accumulator (e.g. into an RCCL send buffer), ordered against the
  * caller's HIP stream `caller_stream` (NULL: the null stream) without blocking the host: the
  * context's stream first waits for the work queued on caller_stream so far (a fill of dst, a
