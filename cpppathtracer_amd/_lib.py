@@ -101,6 +101,10 @@ PROTOTYPES = {
     "cpt_last_reproject_ms": (_I, [_P, _P]),
     "cpt_last_reproject_launch_ms": (_I, [_P, _P]),
     "cpt_reproject_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_float, _P]),
+    "cpt_denoise_mix_history": (_I, [_P, _P]),
+    "cpt_read_display_count": (_I, [_P, _P, _SZ]),
+    "cpt_reproject_display": (_I, [_P, _P, _P, _I, ctypes.c_float, _U32]),
+    "cpt_reproject_display_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_float, _P, _P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1

@@ -578,12 +578,67 @@ void PathTracer::PipelineLoop() {
         bool ok;
         {
             std::lock_guard<std::mutex> lk(mu_);
-            ok = RenderPass(cma, 1, false);
-            if (ok && cpt_denoise_mix(FrameCtx(), cma.cur_sample_idx_, output_buffer_.data()) != CPT_OK)
-                ok = Fail("cpt_denoise_mix");
+            if (display_reproject_) {
+                ok = DisplayPassWithHistory(cma);
+            } else {
+                ok = RenderPass(cma, 1, false);
+                if (ok && cpt_denoise_mix(FrameCtx(), cma.cur_sample_idx_, output_buffer_.data()) != CPT_OK)
+                    ok = Fail("cpt_denoise_mix");
+            }
         }
         if (ok && task.Callback) task.Callback(output_buffer_.data(), width_, height_, task.cbParam);
     }
+}
+
+bool PathTracer::SetDisplayReprojection(bool on, int max_history, float plane_tol) {
+    std::lock_guard<std::mutex> lk(mu_);
+    // what cpt_reproject_display would refuse at every Refresh is refused here, once
+    if (max_history < 1 || !(plane_tol >= 0.f) || !(plane_tol - plane_tol == 0.f)) {
+        err_ = "SetDisplayReprojection: max_history " + std::to_string(max_history) + " (>= 1), plane_tol " +
+               std::to_string(plane_tol) + " (finite, >= 0)";
+        return false;
+    }
+    display_reproject_ = on;
+    display_max_history_ = max_history;
+    display_plane_tol_ = plane_tol;
+    prev_pass_ = false;   // the first pass after a switch restarts
+    return true;
+}
+
+// One pass of the loop with SetDisplayReprojection on (mu_ held): after a Refresh the display
+// state moves to the new camera, or restarts where it cannot; then the pass and the per-pixel Mix.
+// A pass that neither follows a Refresh nor a pass of this kind joins the mean the loop has so far
+// through cpt_denoise_mix at the camera's index, which the per-pixel counts then continue from: the
+// loop's first pass is such a one, its index being 2 after InitBuffers' copy (path_tracer.cu:258),
+// so a still camera's frames are the reference loop's.
+bool PathTracer::DisplayPassWithHistory(MotionalCamera& cma) {
+    const bool had_prev = prev_pass_, refreshed = cma.cur_sample_idx_ == 1;
+    prev_pass_ = false;
+    if (!SyncScene() || !EnsureFrame(cma)) return false;
+    if (refreshed) {
+        const Tile& t0 = tiles_[0];
+        // (a frame under 16 pixels either way has no launch region: no display pass ever ran there)
+        const bool carry = had_prev && prev_cam_.width_ == width_ && prev_cam_.height_ == height_ && width_ >= 16 &&
+                           height_ >= 16 && t0.scene_build == prev_scene_build_ && t0.scene_rev == prev_scene_rev_ && !frame_;
+        if (carry) {
+            if (cpt_reproject_display(t0.ctx, reinterpret_cast<const cpt_camera*>(&prev_cam_), reinterpret_cast<const cpt_camera*>(&cma),
+                                      display_max_history_, display_plane_tol_, ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK)
+                return Fail("cpt_reproject_display", t0.ctx);
+        } else if (cpt_reset_display(FrameCtx()) != CPT_OK) {
+            return Fail("cpt_reset_display");
+        }
+    }
+    if (!RenderPass(cma, 1, false)) return false;
+    if (!refreshed && !had_prev) {
+        if (cpt_denoise_mix(FrameCtx(), cma.cur_sample_idx_, output_buffer_.data()) != CPT_OK) return Fail("cpt_denoise_mix");
+    } else if (cpt_denoise_mix_history(FrameCtx(), output_buffer_.data()) != CPT_OK) {
+        return Fail("cpt_denoise_mix_history");
+    }
+    prev_cam_ = cma;
+    prev_scene_build_ = tiles_[0].scene_build;
+    prev_scene_rev_ = tiles_[0].scene_rev;
+    prev_pass_ = true;
+    return true;
 }
 
 void PathTracer::Stop() {

@@ -84,6 +84,18 @@ struct DisplayBand {
     DevBuf<uint8_t> d_bgra;    // the display frame (band rows)
     DevBuf<float4> d_sink;     // k_denoise_strip: where lanes without an output pixel store (DN_SINK_SLOTS)
     int y0 = -1, y1 = -1;      // the band the buffers hold
+    // The per-pixel display history (cpt_denoise_mix_history, cpt_reproject_display):
+    // each pixel's sample count beside d_mix, an integer held as a float.  cpt_denoise_mix[_band]
+    // does not write it: it records its index and marks the plane stale, and the next reader of
+    // the plane first fills the launch region with that index (fill_count).
+    DevBuf<float> d_count;
+    uint32_t last_idx = 0;     // the last recorded global index (0: none since the planes were zeroed)
+    bool count_stale = false;
+    // the planes the next cpt_reproject_display writes; swapped with d_mix / d_count behind it
+    DevBuf<float> d_mix_next, d_count_next;
+
+    // the count plane brought up to date on the context's stream (cpt_capi_display.cpp)
+    int fill_count(cpt_ctx* c);
 };
 
 // The adaptive render (cpt_capi_adaptive.cpp; allocated on the frame's first cpt_render_adaptive).
@@ -136,7 +148,8 @@ struct GBufferState {
     bool valid = false;                 // a cpt_gbuffer has been queued since cpt_set_frame
 };
 
-// The reprojection (cpt_capi_reproject.cpp; allocated on the frame's first cpt_reproject_accum).
+// The reprojection (cpt_capi_reproject.cpp; allocated on the frame's first cpt_reproject_accum or
+// cpt_reproject_display, which uses the history's id and distance planes).
 struct ReprojectState {
     DevBuf<int32_t> d_id;      // the G-buffer at the camera the history was rendered with: object
     DevBuf<float> d_t;         // index and hit distance per pixel
@@ -180,7 +193,7 @@ struct cpt_ctx {
     TimedSpan t_display;   // the last display kernel (k_denoise_rows)
     TimedSpan t_filter;    // the last cpt_filter_frame's launches
     TimedSpan t_query;     // the last query kernel (cpt_gbuffer, cpt_trace_rays, cpt_pick)
-    TimedSpan t_reproject; // the last cpt_reproject_accum's launches ...
+    TimedSpan t_reproject; // the last cpt_reproject_accum's or cpt_reproject_display's launches ...
     DevEvent ev_reproject[2];   // ... and the two points between them: after each G-buffer trace
     std::string err;
 
@@ -282,10 +295,14 @@ namespace ctx {
 
 // CPT_ERR_STATE from `who` while an adaptive render is pending on the context (between
 // cpt_adaptive_begin and the cpt_adaptive_step that returns 0): its rounds own the frame's buffers.
-#define CPT_REFUSE_PENDING(ctx, who)                                                                              \
-    do {                                                                                                          \
-        if ((ctx)->frame.adaptive.pending.on)                                                                           \
-            return fail((ctx), CPT_ERR_STATE, who ": an adaptive render is pending (cpt_adaptive_step until 0)"); \
+// CPT_OK otherwise.  The refusal is written here alone; the macro returns it from the caller.
+inline int refuse_pending(cpt_ctx* c, const char* who) {
+    if (!c->frame.adaptive.pending.on) return CPT_OK;
+    return fail(c, CPT_ERR_STATE, "%s: an adaptive render is pending (cpt_adaptive_step until 0)", who);
+}
+#define CPT_REFUSE_PENDING(ctx, who)                             \
+    do {                                                         \
+        if (int rc_ = refuse_pending((ctx), (who))) return rc_;  \
     } while (0)
 
 // Drain the context's stream, then report a device-side error of the work it ran.

@@ -5,6 +5,8 @@
 //   k_selftest_dn_weight  its exhaustive check (cpt_selftest_qdiv which = 6, 7), beside the code
 //                         it checks so the 8 KB table exists once
 //   k_denoise_rows        Denoising + Mix (path_tracer.cu:177-254);  launch_denoise_mix
+//                         <HOST, HIST>: HIST the same with a per-pixel Mix weight (cpt_denoise_mix_history)
+//   k_fill_count          the count plane's fill;  launch_fill_count
 //   k_stitch_rows         the row-tile gather (cpt_gather_rows);  launch_stitch_rows
 //   k_stitch_moments      the gather of a source's adaptive moments;  launch_stitch_moments
 //
@@ -263,6 +265,9 @@ hipError_t launch_selftest_dn_weight(int which, uint64_t n, unsigned long long* 
 // stored as weight 0 so the taps need no branch (138 VGPRs) 0.097; 8-wave blocks at 4 waves per
 // SIMD, batches of 4 pair weights and the loads issued after the pair weights (124 VGPRs, no
 // spill) 0.090-0.092 (with the loads ahead of the pairs: 14 VGPRs spilled, 0.093-0.099).
+// Those are round 5's registers.  Under the build's iterative-maxocc scheduler (build.py) and the
+// current compiler every instantiation, HIST or not, has 128 VGPRs with 10 spilled to 28 B of
+// scratch (profiles/r14/isa_compare.log), at the times of §11.3.
 // Loads are issued unconditionally (out-of-frame lanes read a valid address and discard it)
 // and the stores sit in a branch-free tail (lanes without an output pixel store to `sink`), so
 // the next row's wait does not drain a branch's worth of stores.
@@ -277,11 +282,16 @@ constexpr size_t DNR_LDS_BYTES = DN_EXP_N * sizeof(double) + 2 * DNR_PIX_ROWS * 
                                  DNR_W_ROWS * 12 * DNS_LANES * sizeof(float);
 static_assert(DNR_LDS_BYTES * DNR_BLOCKS_PER_CU <= 160 * 1024, "k_denoise_rows: blocks per CU exceed the CU's LDS");
 
-template <bool HOST>
+// HIST (cpt_denoise_mix_history): Mix weighs each pixel by its own sample count n,
+// read from `count` with the output row's mix and stored back as n + 1, in place of the frame's
+// one 1 / cur_sample_idx: inv = 1 / (n + 1), the same correctly rounded quotient where n + 1 is
+// that index.  Without it `count` is not read and the code is the kernel's as it was.
+template <bool HOST, bool HIST>
 __global__ void __launch_bounds__(DNS_LANES * DNR_WAVES, DNR_MINWAVES) k_denoise_rows(
     const float4* __restrict__ accum, const float* __restrict__ normal, const float* __restrict__ depth,
     float* __restrict__ mix, uint8_t* __restrict__ out, uint8_t* __restrict__ out_host, float4* __restrict__ sink,
-    int width, int row0, int ctx_rows, int y0, int y1, int w_eff, int h_eff, int n_strips, int per_strip, float inv_idx) {
+    int width, int row0, int ctx_rows, int y0, int y1, int w_eff, int h_eff, int n_strips, int per_strip, float inv_idx,
+    float* __restrict__ count) {
     __shared__ double s_tab[DN_EXP_N];
     __shared__ float4 rgbv[DNR_PIX_ROWS][DNS_LANES];
     __shared__ float4 ndr[DNR_PIX_ROWS][DNS_LANES];
@@ -344,11 +354,13 @@ __global__ void __launch_bounds__(DNS_LANES * DNR_WAVES, DNR_MINWAVES) k_denoise
         const int R = B + wv;           // this wave's new row
         const int O = R - 2;            // the output row it finalizes
         float3 mix_cur;
+        float cnt_cur = 0.f;
         auto load_mix = [&]() {
             const int orow = min(max(O, ra), rb - 1);
             const int ocol = min(max(col, 0), w_eff - 1);
             const size_t b = (size_t)(orow - y0) * width + ocol;
             mix_cur = make_float3(mix[3 * b], mix[3 * b + 1], mix[3 * b + 2]);
+            if (HIST) cnt_cur = count[b];
         };
         put(R, na, nn, nd, nvalid);
         const DnsPix me = ring(R, j);   // (this lane's own write: ordered)
@@ -429,7 +441,8 @@ __global__ void __launch_bounds__(DNS_LANES * DNR_WAVES, DNR_MINWAVES) k_denoise
             const v3 clp = mk(__builtin_fmaxf(0.f, __builtin_fminf(dn.x, 1.f)), __builtin_fmaxf(0.f, __builtin_fminf(dn.y, 1.f)),
                               __builtin_fmaxf(0.f, __builtin_fminf(dn.z, 1.f)));
             v3 m = mk(mix_cur.x, mix_cur.y, mix_cur.z);
-            m = m + inv_idx * (clp - m);   // lerp (helper_math.h:1154-1157)
+            // (HIST: the weight is formed here, from the count, not held through the taps)
+            m = m + (HIST ? 1.f / (cnt_cur + 1.f) : inv_idx) * (clp - m);   // lerp (helper_math.h:1154-1157)
             st_m = m;
             st_bgr = (uint32_t)(uint8_t)(255.99f * m.z) | ((uint32_t)(uint8_t)(255.99f * m.y) << 8) |
                      ((uint32_t)(uint8_t)(255.99f * m.x) << 16);
@@ -443,6 +456,10 @@ __global__ void __launch_bounds__(DNS_LANES * DNR_WAVES, DNR_MINWAVES) k_denoise
             pm[1] = st_m.y;
             pm[2] = st_m.z;
             *po = st_bgr;
+            if (HIST) {
+                float* const pc = st_real ? count + bself : reinterpret_cast<float*>(sink_lane);
+                *pc = cnt_cur + 1.f;
+            }
             if (HOST) {
                 uint32_t* const ph = st_real ? reinterpret_cast<uint32_t*>(out_host) + bself : reinterpret_cast<uint32_t*>(sink_lane) + 3;
                 *ph = st_bgr;
@@ -451,23 +468,44 @@ __global__ void __launch_bounds__(DNS_LANES * DNR_WAVES, DNR_MINWAVES) k_denoise
     }
 }
 
-hipError_t launch_denoise_mix(const float4* accum, const float* normal, const float* depth, float* mix, uint8_t* out,
-                              uint8_t* out_host, float4* sink, int width, int height, int row0, int ctx_rows, int y0, int y1,
-                              uint32_t cur_sample_idx, const LaunchGrid& grid, hipStream_t stream) {
+// count != nullptr: the per-pixel Mix, which does not read cur_sample_idx.
+hipError_t launch_denoise_mix(const float4* accum, const float* normal, const float* depth, float* mix, float* count,
+                              uint8_t* out, uint8_t* out_host, float4* sink, int width, int height, int row0, int ctx_rows, int y0,
+                              int y1, uint32_t cur_sample_idx, const LaunchGrid& grid, hipStream_t stream) {
     const int w_eff = 16 * (width / 16), h_eff = 16 * (height / 16);
     if (w_eff == 0 || h_eff == 0 || y1 <= y0) return hipSuccess;
-    const float inv_idx = 1.f / float(cur_sample_idx);
     const int n_strips = (w_eff + DNS_COLS - 1) / DNS_COLS;
     const int rows = y1 - y0;
     int per_strip = (grid.cus * DNR_BLOCKS_PER_CU + n_strips - 1) / n_strips;
     per_strip = per_strip < 1 ? 1 : (per_strip > rows ? rows : per_strip);
     const unsigned blocks = (unsigned)(n_strips * per_strip);
-    if (out_host)
-        hipLaunchKernelGGL(k_denoise_rows<true>, dim3(blocks), dim3(DNS_LANES * DNR_WAVES), 0, stream, accum, normal, depth, mix,
-                           out, out_host, sink, width, row0, ctx_rows, y0, y1, w_eff, h_eff, n_strips, per_strip, inv_idx);
-    else
-        hipLaunchKernelGGL(k_denoise_rows<false>, dim3(blocks), dim3(DNS_LANES * DNR_WAVES), 0, stream, accum, normal, depth, mix,
-                           out, out_host, sink, width, row0, ctx_rows, y0, y1, w_eff, h_eff, n_strips, per_strip, inv_idx);
+    const float inv_idx = count ? 0.f : 1.f / float(cur_sample_idx);
+    const dim3 grid_dim(blocks), block_dim(DNS_LANES * DNR_WAVES);
+#define CPT_DN_LAUNCH(HOST, HIST)                                                                                             \
+    hipLaunchKernelGGL((k_denoise_rows<HOST, HIST>), grid_dim, block_dim, 0, stream, accum, normal, depth, mix, out, out_host, \
+                       sink, width, row0, ctx_rows, y0, y1, w_eff, h_eff, n_strips, per_strip, inv_idx, count)
+    if (count) {
+        if (out_host) CPT_DN_LAUNCH(true, true);
+        else CPT_DN_LAUNCH(false, true);
+    } else {
+        if (out_host) CPT_DN_LAUNCH(true, false);
+        else CPT_DN_LAUNCH(false, false);
+    }
+#undef CPT_DN_LAUNCH
+    return hipGetLastError();
+}
+
+// The count plane's fill (a switch from cpt_denoise_mix to the per-pixel Mix): `value` in the
+// first w_eff columns of `rows` rows of `width` floats.  One lane per float.
+__global__ void __launch_bounds__(256) k_fill_count(float* __restrict__ count, int width, int w_eff, int rows, float value) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y;
+    if (x < w_eff && y < rows) count[(size_t)y * width + x] = value;
+}
+
+hipError_t launch_fill_count(float* count, int width, int w_eff, int rows, float value, hipStream_t stream) {
+    if (w_eff <= 0 || rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fill_count, dim3((w_eff + 255) / 256, rows), dim3(256), 0, stream, count, width, w_eff, rows, value);
     return hipGetLastError();
 }
 

@@ -257,8 +257,12 @@ hipError_t launch_stitch_moments(const float* src, size_t src_npix, const int32_
 // normal / depth hold the context's ctx_rows rows from row0; sink: a
 // device buffer of DN_SINK_SLOTS float4s the strip kernel's lanes without an output pixel store to
 constexpr int DN_SINK_SLOTS = 1024 * 64;
-hipError_t launch_denoise_mix(const float4* accum, const float* normal, const float* depth, float* mix, uint8_t* out,
-                              uint8_t* out_host, float4* sink, int width, int height, int row0, int ctx_rows, int y0, int y1,
-                              uint32_t cur_sample_idx, const LaunchGrid& grid, hipStream_t stream);
+// count == nullptr: Mix at 1 / cur_sample_idx; else the per-pixel Mix on that count plane (beside
+// mix, one float per pixel), which does not read cur_sample_idx
+hipError_t launch_denoise_mix(const float4* accum, const float* normal, const float* depth, float* mix, float* count,
+                              uint8_t* out, uint8_t* out_host, float4* sink, int width, int height, int row0, int ctx_rows, int y0,
+                              int y1, uint32_t cur_sample_idx, const LaunchGrid& grid, hipStream_t stream);
+// `value` into the first w_eff columns of `rows` rows of a count plane of `width` columns
+hipError_t launch_fill_count(float* count, int width, int w_eff, int rows, float value, hipStream_t stream);
 
 }  // namespace cpt

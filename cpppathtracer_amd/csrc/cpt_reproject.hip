@@ -9,6 +9,13 @@
 //                       direction ray_gen_centre of the old camera; the output is one 16-byte
 //                       store per lane, to a second plane (taps read neighbours).  No LDS.
 //
+//   k_reproject_display the same shape for cpt_reproject_display: the display
+//                       state, the Mix mean and the per-pixel sample count, looked up at the moved
+//                       camera.  A tap is three 4-byte mean loads and the count, id and distance
+//                       gathers; the output is three 4-byte mean stores and the count, to second
+//                       planes.  Every pixel of the frame is written (zeros outside the display's
+//                       launch region).  No LDS.
+//
 // The reference has no counterpart (MotionalCamera::Refresh restarts the running mean).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,6 +47,19 @@ struct DeviceSrc {
     __device__ rp::V3 dir0(int x, int y, size_t) const { return as_v3(ray_gen_centre(*cam0, x, y).d); }
 };
 
+// The old frame's display state in device memory.
+struct DeviceDisplaySrc {
+    const float* mean;
+    const float* count;
+    const int32_t* id;
+    const float* t;
+    const CamK* cam0;
+    __device__ rp::Px shown(size_t k) const { return rp::Px{mean[3 * k], mean[3 * k + 1], mean[3 * k + 2], count[k]}; }
+    __device__ int32_t id0(size_t k) const { return id[k]; }
+    __device__ float t0(size_t k) const { return t[k]; }
+    __device__ rp::V3 dir0(int x, int y, size_t) const { return as_v3(ray_gen_centre(*cam0, x, y).d); }
+};
+
 }  // namespace
 
 __global__ void __launch_bounds__(256) k_reproject_accum(const ReprojectArgs a) {
@@ -54,6 +74,30 @@ __global__ void __launch_bounds__(256) k_reproject_accum(const ReprojectArgs a) 
     const rp::Px r = rp::pixel(src, a.view0, o1, a.width, a.height, a.id1[pix], a.t1[pix], n1,
                                as_v3(ray_gen_centre(a.cam1, x, y).d), a.max_history, a.plane_tol);
     a.out[pix] = make_float4(r.r, r.g, r.b, r.n);
+}
+
+__global__ void __launch_bounds__(256) k_reproject_display(const ReprojectDisplayArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const TileGrid grid{a.width, a.height};
+    int x = 0, y = 0;
+    if ((i >> 6) >= (uint32_t)grid.count() || !grid.pixel(i >> 6, i & 63, x, y)) return;
+    const size_t pix = (size_t)y * a.width + x;
+    const DeviceDisplaySrc src{a.mean_in, a.count_in, a.id0, a.t0, &a.cam0};
+    const rp::V3 n1{a.normal1[3 * pix], a.normal1[3 * pix + 1], a.normal1[3 * pix + 2]};
+    const rp::V3 o1{a.cam1.origin[0], a.cam1.origin[1], a.cam1.origin[2]};
+    const rp::Px r = rp::display_pixel(src, a.view0, o1, a.width, a.height, a.w_eff, a.h_eff, x, y, a.id1[pix], a.t1[pix], n1,
+                                       as_v3(ray_gen_centre(a.cam1, x, y).d), a.max_history, a.plane_tol);
+    a.mean_out[3 * pix] = r.r;
+    a.mean_out[3 * pix + 1] = r.g;
+    a.mean_out[3 * pix + 2] = r.b;
+    a.count_out[pix] = r.n;
+}
+
+hipError_t launch_reproject_display(const ReprojectDisplayArgs& a, hipStream_t stream) {
+    const size_t lanes = (size_t)TileGrid{a.width, a.height}.count() * 64;
+    if (lanes == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_reproject_display, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_reproject(const ReprojectArgs& a, hipStream_t stream) {

@@ -1,5 +1,6 @@
-// cpt_reproject.hpp — reprojection of the accumulated frame to a moved camera,
-// shared by the device (cpt_reproject.hip) and the host (cpt_reproject_host).
+// cpt_reproject.hpp — reprojection of the accumulated frame and of the display's
+// running mean with its per-pixel sample counts (§22) to a moved camera, shared by the device
+// (cpt_reproject.hip) and the host (cpt_reproject_host, cpt_reproject_display_host).
 //
 // Backward reprojection: the new pixel's first hit (or, for the sky, its direction as a point at
 // infinity) is projected into the camera the history was rendered with, and the four accumulator
@@ -104,12 +105,26 @@ __host__ __device__ inline float snap(float f) {
     return d <= SNAP ? r : f;
 }
 
-// One output pixel.  `src` gives the old frame: src.accum(k), src.id0(k), src.t0(k) and
-// src.dir0(x, y, k) of a pixel k = y * width + x inside it.  id1, t1, n1 and d1 are the new
-// pixel's G-buffer entry and centre-ray direction, o1 the new camera's origin.
-template <typename Src>
+// A tap's history: the accumulator's pixel or, DISPLAY, the display state's.
+template <bool DISPLAY, typename Src>
+__host__ __device__ inline Px history(const Src& src, size_t k) {
+    if constexpr (DISPLAY) return src.shown(k);
+    else return src.accum(k);
+}
+
+// One output pixel of the accumulator, (rgb sums, integer pass count), or, DISPLAY, of the display
+// state (`display_pixel` below).  The geometry is written once, here, for both: the projection
+// through OldView, the snap, the frame bounds, the id test, the tangent-plane test; the two differ
+// in what a tap holds and how it is blended.  `src` gives the old frame: src.id0(k), src.t0(k) and
+// src.dir0(x, y, k) of a pixel k = y * width + x inside it, and its history, src.accum(k) (rgb sums,
+// pass count) or, DISPLAY, src.shown(k) (the Mix mean's rgb, sample count), of which only taps
+// inside w_eff x h_eff count.  id1, t1, n1 and d1 are the new pixel's G-buffer entry and centre-ray
+// direction, o1 the new camera's origin.  One body and no wrapper on the accumulator's side: its
+// instantiation compiles to the kernel it was before the display look-up joined it (§22).
+template <bool DISPLAY = false, typename Src>
 __host__ __device__ inline Px pixel(const Src& src, const OldView& v, const V3& o1, int width, int height, int32_t id1,
-                                    float t1, const V3& n1, const V3& d1, float max_history, float plane_tol) {
+                                    float t1, const V3& n1, const V3& d1, float max_history, float plane_tol, int w_eff = 0,
+                                    int h_eff = 0) {
 #pragma clang fp contract(off)
     const Px none{0.0f, 0.0f, 0.0f, 0.0f};
     const bool hit = id1 >= 0;
@@ -130,9 +145,11 @@ __host__ __device__ inline Px pixel(const Src& src, const OldView& v, const V3& 
         for (int a = 0; a < 2; ++a) {
             const int x = x0 + a, y = y0 + b;
             if (x < 0 || x >= width || y < 0 || y >= height) continue;
+            if constexpr (DISPLAY)
+                if (x >= w_eff || y >= h_eff) continue;
             const size_t k = (size_t)y * width + x;
             if (src.id0(k) != id1) continue;
-            const Px A = src.accum(k);
+            const Px A = history<DISPLAY>(src, k);
             if (!(A.n >= 1.0f) || !finite(A.r) || !finite(A.g) || !finite(A.b)) continue;
             if (hit) {
                 // the tap's own hit point lies on the new hit's tangent plane
@@ -141,19 +158,37 @@ __host__ __device__ inline Px pixel(const Src& src, const OldView& v, const V3& 
                 if (!(pd <= bound)) continue;
             }
             const float wgt = (a ? wx : 1.0f - wx) * (b ? wy : 1.0f - wy);
-            // the one tap of weight 1, within the cap: its float4 as it is
+            // the one tap of weight 1, within the cap: its four floats as they are
             if (wgt == 1.0f && A.n <= max_history) return A;
             Wt += wgt;
-            sr += wgt * (A.r / A.n);
-            sg += wgt * (A.g / A.n);
-            sb += wgt * (A.b / A.n);
+            if constexpr (DISPLAY) {   // the mean as it is
+                sr += wgt * A.r;
+                sg += wgt * A.g;
+                sb += wgt * A.b;
+            } else {                   // sums: the mean of A.n passes
+                sr += wgt * (A.r / A.n);
+                sg += wgt * (A.g / A.n);
+                sb += wgt * (A.b / A.n);
+            }
             sn += wgt * A.n;
         }
     if (!(Wt >= MIN_WEIGHT)) return none;
     const float n = sn / Wt;
     const float cap = floorf(n < max_history ? n : max_history);
     if (!(cap >= 1.0f)) return none;
-    return Px{(sr / Wt) * cap, (sg / Wt) * cap, (sb / Wt) * cap, cap};
+    if constexpr (DISPLAY) return Px{sr / Wt, sg / Wt, sb / Wt, cap};
+    else return Px{(sr / Wt) * cap, (sg / Wt) * cap, (sb / Wt) * cap, cap};
+}
+
+// One output pixel (x1, y1) of the display state (cpt_reproject_display): (the Mix
+// mean's rgb, the sample count).  The display's launch region is w_eff x h_eff: a pixel outside it
+// holds nothing, a tap outside it does not count; the mean is blended as it is, the count beside it.
+template <typename Src>
+__host__ __device__ inline Px display_pixel(const Src& src, const OldView& v, const V3& o1, int width, int height, int w_eff,
+                                            int h_eff, int x1, int y1, int32_t id1, float t1, const V3& n1, const V3& d1,
+                                            float max_history, float plane_tol) {
+    if (x1 >= w_eff || y1 >= h_eff) return Px{0.0f, 0.0f, 0.0f, 0.0f};
+    return pixel<true>(src, v, o1, width, height, id1, t1, n1, d1, max_history, plane_tol, w_eff, h_eff);
 }
 
 // The old frame as plain arrays (the host entry).
@@ -163,6 +198,19 @@ struct PlaneSrc {
     const float* t;
     const float* dir3;
     __host__ __device__ Px accum(size_t k) const { return in[k]; }
+    __host__ __device__ int32_t id0(size_t k) const { return id[k]; }
+    __host__ __device__ float t0(size_t k) const { return t[k]; }
+    __host__ __device__ V3 dir0(int, int, size_t k) const { return V3{dir3[3 * k], dir3[3 * k + 1], dir3[3 * k + 2]}; }
+};
+
+// The old frame's display state as plain arrays (the host entry): mean [npix][3], count [npix].
+struct DisplayPlaneSrc {
+    const float* mean3;
+    const float* count;
+    const int32_t* id;
+    const float* t;
+    const float* dir3;
+    __host__ __device__ Px shown(size_t k) const { return Px{mean3[3 * k], mean3[3 * k + 1], mean3[3 * k + 2], count[k]}; }
     __host__ __device__ int32_t id0(size_t k) const { return id[k]; }
     __host__ __device__ float t0(size_t k) const { return t[k]; }
     __host__ __device__ V3 dir0(int, int, size_t k) const { return V3{dir3[3 * k], dir3[3 * k + 1], dir3[3 * k + 2]}; }
@@ -188,5 +236,25 @@ struct ReprojectArgs {
     float max_history, plane_tol;
 };
 hipError_t launch_reproject(const ReprojectArgs& a, hipStream_t stream);
+
+// k_reproject_display's arguments: the same cameras and G-buffer planes; the display state of the
+// width x height frame (the Mix mean [npix][3] and the count plane [npix], of which the launch
+// region w_eff x h_eff is used) and the planes the result goes to (not the same).
+struct ReprojectDisplayArgs {
+    CamK cam0, cam1;
+    reproject::OldView view0;
+    int width, height, w_eff, h_eff;
+    const int32_t* id0;
+    const float* t0;
+    const int32_t* id1;
+    const float* t1;
+    const float* normal1;
+    const float* mean_in;
+    const float* count_in;
+    float* mean_out;
+    float* count_out;
+    float max_history, plane_tol;
+};
+hipError_t launch_reproject_display(const ReprojectDisplayArgs& a, hipStream_t stream);
 
 }  // namespace cpt

@@ -57,6 +57,25 @@ def reproject_host(cam0, cam1, dir0, dir1, id0, t0, id1, t1, normal1, accum, max
     return out
 
 
+def reproject_display_host(cam0, cam1, dir0, dir1, id0, t0, id1, t1, normal1, mean, count, max_history=32, plane_tol=1e-2):
+    """cpt_reproject_display_host (no GPU): the function reproject_display's kernel runs, on host
+    arrays shaped as reproject_host's, with the display state (mean [npix, 3], count [npix]) in
+    place of the accumulator.  Returns the new (mean [npix, 3], count [npix])."""
+    L = _lib.load()
+    a = np.ascontiguousarray(np.array(cam0, dtype=CAMERA_DTYPE))
+    b = np.ascontiguousarray(np.array(cam1, dtype=CAMERA_DTYPE))
+    W, H = int(a["width"].reshape(-1)[0]), int(a["height"].reshape(-1)[0])
+    n = W * H
+    f32 = lambda v, shape: np.ascontiguousarray(v, dtype=np.float32).reshape(shape)
+    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32).reshape(n)
+    d0, d1, nn, m, c = f32(dir0, (n, 3)), f32(dir1, (n, 3)), f32(normal1, (n, 3)), f32(mean, (n, 3)), f32(count, n)
+    i0, i1, tt0, tt1 = i32(id0), i32(id1), f32(t0, n), f32(t1, n)
+    mean_out, count_out = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.float32)
+    check(L.cpt_reproject_display_host(_p(a), _p(b), W, H, _p(d0), _p(d1), _p(i0), _p(tt0), _p(i1), _p(tt1), _p(nn), _p(m), _p(c),
+                                       int(max_history), ctypes.c_float(plane_tol), _p(mean_out), _p(count_out)))
+    return mean_out, count_out
+
+
 class Renderer:
     def __init__(self, device: int = 0):
         self._L = _lib.load()
@@ -344,8 +363,19 @@ class Renderer:
         self._check(self._L.cpt_reproject_accum(self._ctx, _p(a), _p(b), int(max_history), ctypes.c_float(plane_tol),
                                                 int(flags)))
 
+    def reproject_display(self, cam_from, cam_to, max_history=32, plane_tol=1e-2, flags=0):
+        """cpt_reproject_display: reproject_accum's look-up applied to the display state, the Mix
+        running mean and the per-pixel sample counts of denoise_mix_history, which the next
+        denoise_mix_history continues from.  Needs a display pass of the full frame; leaves the
+        accumulator, the RNG and the BGRA8 frame alone and cam_to's G-buffer in read_gbuffer.
+        Asynchronous."""
+        a = np.ascontiguousarray(np.array(cam_from, dtype=CAMERA_DTYPE))
+        b = np.ascontiguousarray(np.array(cam_to, dtype=CAMERA_DTYPE))
+        self._check(self._L.cpt_reproject_display(self._ctx, _p(a), _p(b), int(max_history), ctypes.c_float(plane_tol),
+                                                  int(flags)))
+
     def last_reproject_ms(self, split=False):
-        """Device time of the last reproject_accum, all its launches (HIP events); waits for it.
+        """Device time of the last reproject_accum or reproject_display, all its launches (HIP events); waits for it.
         split: (trace at cam_from, trace at cam_to, look-up kernel) instead of their total."""
         if split:
             ms3 = (ctypes.c_float * 3)()
@@ -558,6 +588,33 @@ class Renderer:
         if not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
             raise ValueError("denoise_mix: `out` must be C-contiguous and writeable")
         self._check(self._L.cpt_denoise_mix(self._ctx, cur_sample_idx, _p(out)))
+        return out
+
+    def denoise_mix_history(self, out=None, host=True):
+        """cpt_denoise_mix_history: denoise_mix with each pixel mixed at 1 / (its own sample count
+        + 1), the count kept beside the running mean (read_display_count); `out` and `host` as
+        denoise_mix's.  From a reset display, k calls equal denoise_mix(1), ..., denoise_mix(k)."""
+        if not host:
+            self._check(self._L.cpt_denoise_mix_history(self._ctx, None))
+            return None
+        if out is None:
+            out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        if not isinstance(out, np.ndarray) or out.dtype != np.uint8:
+            raise ValueError("denoise_mix_history: `out` must be a numpy uint8 array")
+        if out.size != self.height * self.width * 4:
+            raise ValueError(f"denoise_mix_history: `out` holds {out.size} bytes, the frame needs "
+                             f"{self.height * self.width * 4}")
+        if not out.flags["C_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+            raise ValueError("denoise_mix_history: `out` must be C-contiguous and writeable")
+        self._check(self._L.cpt_denoise_mix_history(self._ctx, _p(out)))
+        return out
+
+    def read_display_count(self):
+        """The per-pixel sample counts of the display band (cpt_read_display_count):
+        [(y1 - y0) * width] float32 holding integers, 0 outside the launch region."""
+        y0, y1 = self.display_band()
+        out = np.zeros((y1 - y0) * self.width, dtype=np.float32)
+        self._check(self._L.cpt_read_display_count(self._ctx, _p(out), out.size))
         return out
 
     def display_band(self):

@@ -5,6 +5,13 @@
 //                [--out radiance.bin] [--dispatch K --bgra frame.bin] [--pfm image.pfm]
 //                [--texture file.ppm|file.cptex] [--dump-scene objects.bin] [--devices N]
 //                [--objects N] [--animate K] [--pick X,Y] [--orbit N [--reproject]]
+//                [--orbit N --display-reproject on|off --bgra frame.bin]
+//
+// --orbit N --display-reproject on|off drives the DispatchRay pipeline through the same orbit: --spp
+// passes at each of the N cameras (each waited for), every move followed by MotionalCamera::Refresh
+// as the reference's viewer does, and writes the last BGRA8 frame to --bgra.  `on` sets
+// PathTracer::SetDisplayReprojection, which carries the running mean to each new camera; `off` is
+// the reference's loop, a fresh mean after every move.
 //
 // --orbit N renders N frames of --spp passes each into one accumulator while the camera turns about
 // the vertical axis through its look-at point, one degree per frame.  Without --reproject the
@@ -166,6 +173,7 @@ int main(int argc, char** argv) {
     int filter_levels = -1;
     int orbit = 0;
     bool reproject = false;
+    std::string display_reproject;   // "", "on" or "off"
     for (int i = 1; i < argc; i += 2) {
         std::string k = argv[i];
         if (k == "--filter") {
@@ -198,6 +206,7 @@ int main(int argc, char** argv) {
         else if (k == "--animate") animate = std::stoi(v);
         else if (k == "--pick") pick = v;
         else if (k == "--orbit") orbit = std::stoi(v);
+        else if (k == "--display-reproject") display_reproject = v;
         else if (k == "--adaptive") adaptive = std::stof(v);
         else if (k == "--min-spp") min_spp = std::stoi(v);
         else if (k == "--batch") batch = std::stoi(v);
@@ -262,6 +271,50 @@ int main(int argc, char** argv) {
         const int object = tracer.Pick(px, py, &t);
         if (object < 0 && !tracer.LastError().empty()) { fprintf(stderr, "Pick: %s\n", tracer.LastError().c_str()); return 1; }
         printf("pick (%d, %d): object %d, t %.9g\n", px, py, object, (double)t);
+        return 0;
+    }
+
+    if (!display_reproject.empty()) {
+        if (orbit <= 0 || (display_reproject != "on" && display_reproject != "off")) {
+            fprintf(stderr, "--display-reproject wants on or off, and --orbit N\n");
+            return 2;
+        }
+        FrameSink sink;
+        if (!tracer.SetDisplayReprojection(display_reproject == "on")) {
+            fprintf(stderr, "SetDisplayReprojection: %s\n", tracer.LastError().c_str());
+            return 1;
+        }
+        tracer.InitPipeline();
+        const float c = 0.99984770f, s = 0.01745241f;   // the orbit of --orbit below
+        float dx = cam->origin_.x - cam->look_at_.x, dz = cam->origin_.z - cam->look_at_.z;
+        int sent = 0;
+        for (int f = 0; f < orbit; ++f) {
+            if (f > 0) {
+                const float nx = c * dx + s * dz, nz = c * dz - s * dx;
+                dx = nx;
+                dz = nz;
+                cam->SetOrigin(cam->look_at_.x + dx, cam->origin_.y, cam->look_at_.z + dz);
+                cam->Refresh();
+            }
+            for (int p = 0; p < spp; ++p) {
+                tracer.DispatchRay(DispatchRayArgs{&sink, on_frame});
+                ++sent;
+                const auto t0 = std::chrono::steady_clock::now();
+                while (sink.frames.load() < sent) {
+                    std::this_thread::sleep_for(std::chrono::microseconds(200));
+                    if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(120)) {
+                        fprintf(stderr, "dispatch timeout (%s)\n", tracer.LastError().c_str());
+                        return 1;
+                    }
+                }
+            }
+        }
+        tracer.Stop();
+        printf("orbit: %d cameras of %d display passes, display reprojection %s\n", orbit, spp, display_reproject.c_str());
+        if (!bgra_out.empty()) {
+            std::ofstream f(bgra_out, std::ios::binary);
+            f.write(reinterpret_cast<const char*>(sink.last.data()), (std::streamsize)sink.last.size());
+        }
         return 0;
     }
 

@@ -12,7 +12,7 @@
 //   SetMaxRecursionDepth, SetSeed, SetDevice, SetDevices (row tiling over several GPUs),
 //   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance,
 //   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
-//   Reproject, GetStats, Stop.
+//   Reproject, SetDisplayReprojection, GetStats, Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -113,6 +113,21 @@ public:
     // DispatchRay loop (the Mix running mean with its one global sample index) does not use it.
     // Not available with SetDevices(n > 1): the row tiles own their accumulators (false, LastError).
     bool Reproject(const MotionalCamera& from, int max_history = 32, float plane_tol = 1e-2f);
+    // Keeps the DispatchRay loop's running mean through camera moves (cpt_reproject_display,
+    // cpt_denoise_mix_history).  Off (the default): the loop is the reference's, Mix at
+    // 1 / cur_sample_idx (path_tracer.cu:241-254, 256-306), a raw one-sample frame after every
+    // MotionalCamera::Refresh.  On: every pass displays with the per-pixel Mix, and a pass whose
+    // camera copy has cur_sample_idx_ == 1 (a Refresh happened) first looks the previous pass's mean
+    // and sample counts up at the new camera, provided the previous pass's camera had the frame's
+    // size and the scene has not been edited or rebuilt since that pass; otherwise the display
+    // restarts from zero.  The first pass after this call, unless it follows a Refresh, is mixed at
+    // the camera's index as the reference's is, and the per-pixel counts continue from that index:
+    // a still camera gives the reference's running mean, bit for bit.  max_history and plane_tol as
+    // Reproject's; max_history < 1 or a negative or non-finite plane_tol changes nothing (false,
+    // LastError).  A frame narrower or lower than 16 pixels has no display launch region: its loop
+    // delivers zero frames, on or off.  With SetDevices(n > 1) the frame context holds no scene to
+    // trace, so every Refresh restarts.
+    bool SetDisplayReprojection(bool on, int max_history = 32, float plane_tol = 1e-2f);
     bool GetStats(cpt_stats* out);
     void Stop();                                 // stop the render thread (also in ~PathTracer)
     const std::string& LastError() const { return err_; }
@@ -143,6 +158,7 @@ private:
     bool BindTextures(Tile& t, const std::vector<cpt_object>& objs);
     bool EnsureFrame(const MotionalCamera& cam);
     bool RenderPass(MotionalCamera& cam, int spp, bool accumulate);
+    bool DisplayPassWithHistory(MotionalCamera& cam);
     bool RenderAdaptiveTiles(MotionalCamera& cam, int min_spp, int max_spp, int batch, float rel_error, uint32_t flags,
                              int* rounds, uint64_t* passes_done);
     void PipelineLoop();
@@ -159,6 +175,13 @@ private:
     int width_ = 0, height_ = 0;
     PocaTexture env_ = 0;
     std::shared_ptr<MotionalCamera> camera_;
+    // SetDisplayReprojection, and the previous pass of the loop: its camera copy and scene state
+    bool display_reproject_ = false;
+    int display_max_history_ = 32;
+    float display_plane_tol_ = 1e-2f;
+    bool prev_pass_ = false;
+    MotionalCamera prev_cam_;
+    uint64_t prev_scene_build_ = 0, prev_scene_rev_ = 0;
     std::vector<uint8_t> output_buffer_;   // BGRA8 handed to the callback
     bool output_pinned_ = false;           // output_buffer_ registered with cpt_host_register
     std::string err_;

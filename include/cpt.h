@@ -464,6 +464,39 @@ int cpt_last_reproject_launch_ms(cpt_ctx* ctx, float* ms3);
 int cpt_reproject_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0,
                        const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
                        const float* normal1, const float* accum_in, int max_history, float plane_tol, float* accum_out);
+/* Reprojection of the display state to a moved camera (an addition, DESIGN.md §22: in the
+ * reference's DispatchRay loop every camera move is a MotionalCamera::Refresh and the next Mix runs
+ * at 1 / 1, path_tracer.cu:241-254, so the viewer sees a raw one-sample frame).  The look-up of
+ * cpt_reproject_accum, with the same arguments, geometry and tap tests, applied to the Mix running
+ * mean and the per-pixel sample counts that cpt_denoise_mix_history keeps beside it, not to the
+ * accumulator.  What differs: a tap counts only inside the display's launch region W' x H'
+ * (16*floor(W/16) x 16*floor(H/16)), with a count of at least 1 and a finite mean; the mean is
+ * blended as it is (no division by the count) and the count beside it; a pixel ends as (blended
+ * mean, n) with n = floor(min(blended count, max_history)), or as (0, 0, 0; 0) where less than 1/64
+ * of the bilinear weight was valid, n < 1, or the pixel lies outside W' x H'.  A pixel that maps
+ * exactly onto a valid old pixel of at most max_history samples keeps its mean and count unchanged,
+ * so from == to leaves such a display state bit for bit as it was.  The next
+ * cpt_denoise_mix_history then mixes each pixel at 1 / (its count + 1): pixels with history keep it,
+ * the others restart.
+ * The call traces as cpt_reproject_accum does (cpt_read_gbuffer afterwards returns `to`'s) and
+ * runs the look-up into second mean and count planes that become the display state.  It writes the
+ * display's mean and counts and the G-buffer, and nothing else: the accumulator, RNG states, aux
+ * buffers, moments and filter planes stay, and so does the BGRA8 frame, which changes at the next
+ * display pass.  After cpt_denoise_mix calls the counts are first set to the last cur_sample_idx
+ * (see cpt_denoise_mix_history).  Asynchronous, on the context's stream, ordered like every other
+ * call.  cpt_last_reproject_ms and cpt_last_reproject_launch_ms time the last call of either kind.
+ * Errors: cpt_reproject_accum's, and CPT_ERR_STATE when there has been no display pass since
+ * cpt_set_frame or the display holds a band (cpt_denoise_mix_band) and not the full frame.
+ * Nothing is written on an error.  Limits: cpt_reproject_accum's. */
+int cpt_reproject_display(cpt_ctx* ctx, const cpt_camera* from, const cpt_camera* to, int max_history, float plane_tol,
+                          uint32_t flags);
+/* HOST ONLY, no GPU: the function cpt_reproject_display's kernel runs, shaped like
+ * cpt_reproject_host: mean_in / mean_out [npix][3] and count_in / count_out [npix] (in and out
+ * not the same arrays) in place of the accumulator. */
+int cpt_reproject_display_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0,
+                               const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
+                               const float* normal1, const float* mean_in, const float* count_in, int max_history,
+                               float plane_tol, float* mean_out, float* count_out);
 /* Device-to-device copy of the accumulator (e.g. into an RCCL send buffer), ordered against the
  * caller's HIP stream `caller_stream` (NULL: the null stream) without blocking the host: the
  * context's stream first waits for the work queued on caller_stream so far (a fill of dst, a
@@ -565,6 +598,19 @@ int cpt_last_kernel_stats(cpt_ctx* ctx, float* avg_ms, int* launches);
  * display kernel itself over PCIe; other memory gets a copy after it (the reference's
  * cudaMemcpy, path_tracer.cu:303). */
 int cpt_denoise_mix(cpt_ctx* ctx, uint32_t cur_sample_idx, uint8_t* bgra_host);
+/* cpt_denoise_mix with a Mix weight per pixel (an addition; the reference's Mix has
+ * the frame's one cur_sample_idx, path_tracer.cu:241-254): the display state holds, beside the
+ * running mean, each pixel's sample count n, and the pass mixes at 1 / (n + 1), the correctly
+ * rounded f32 quotient, and stores n + 1.  The stencil, the weights, the clamp, the BGRA8 bytes,
+ * the pinned-host path, the timing (cpt_last_display_ms), the conditions and the error codes are
+ * cpt_denoise_mix's; full frame only.  From a zeroed display state (a new frame,
+ * cpt_reset_display) k calls give the running mean and the bytes of cpt_denoise_mix(1), ..., (k),
+ * bit for bit.  cpt_denoise_mix and cpt_denoise_mix_band do not maintain the counts: they record
+ * their cur_sample_idx, and the first call that reads the counts afterwards (this one,
+ * cpt_reproject_display, cpt_read_display_count) first sets every pixel of the launch region
+ * W' x H' to the last recorded index on the stream, so the two kinds of pass can alternate.  Pixels
+ * outside the launch region hold 0. */
+int cpt_denoise_mix_history(cpt_ctx* ctx, uint8_t* bgra_host);
 /* Pin / unpin a host buffer (hipHostRegister, mapped) so display frames reach it without a
  * staging copy -- e.g. the BGRA8 buffer the reference hands to its per-pass callback
  * (path_tracer.cu:303-304).  Unregister before freeing it. */
@@ -588,12 +634,17 @@ int cpt_display_band(const cpt_ctx* ctx, int* y0, int* y1);
  * `capacity` is rgb's size in floats: CPT_ERR_INVALID_ARG (nothing written) when it is smaller
  * than the band (size it from cpt_display_band). */
 int cpt_read_mix(cpt_ctx* ctx, float* rgb, size_t capacity);
+/* The per-pixel sample counts beside that mean ([(y1-y0)*W] floats holding integers; no reference
+ * counterpart), as cpt_denoise_mix_history and cpt_reproject_display see them: after
+ * cpt_denoise_mix[_band] calls, the last cur_sample_idx inside the launch region.  `capacity` as
+ * cpt_read_mix's, in floats. */
+int cpt_read_display_count(cpt_ctx* ctx, float* count, size_t capacity);
 /* Device time of the last display kernel (Denoising + Mix, the reference's per-pass log of
  * path_tracer.cu:261,300 split by kernel), from HIP events on the context's stream; waits
  * for it. */
 int cpt_last_display_ms(cpt_ctx* ctx, float* ms);
-/* Zero the Mix running mean (the reference's buffer starts uninitialised; here it is zeroed
- * when the frame is created and by this call). */
+/* Zero the Mix running mean and the per-pixel sample counts (the reference's buffer starts
+ * uninitialised; here both are zeroed when the frame is created and by this call). */
 int cpt_reset_display(cpt_ctx* ctx);
 
 /* HBM streaming-read ceiling of the device (the roofline peak, measured on

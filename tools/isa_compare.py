@@ -3,10 +3,16 @@
 by kernel: the instruction stream with its local label numbers normalised, and the register, spill,
 scratch and LDS figures of the code object's metadata.
 
-    tools/isa_compare.py [REV] > profiles/rNN/refactor_isa.log      (REV: the parent, default HEAD)
+    tools/isa_compare.py [REV] [--rename 'OLD=NEW' ...] > profiles/rNN/refactor_isa.log
+                                                                    (REV: the parent, default HEAD)
+
+--rename compares the parent's kernel OLD with the new side's kernel NEW (demangled names, as the log
+prints them): a kernel template that gained a parameter keeps its instantiations under new names.
 
 Both sides are compiled with the flags of cpppathtracer_amd/build.py plus --cuda-device-only -S.
-The log's header names both sides, the compiler and the flags.  Exit status 1 if a kernel's stream
+The log's header names both sides, with the git tree ids of their sources (`git rev-parse
+COMMIT:cpppathtracer_amd/csrc` gives the same id for the commit a side belongs to), the compiler and
+the flags.  Exit status 1 if a kernel's stream
 or figures differ, or it is missing on one side.
 """
 import difflib
@@ -21,7 +27,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 from cpppathtracer_amd import build as _build   # noqa: E402
 
-UNITS = ["cpt_megakernel", "cpt_wavefront", "cpt_query", "cpt_display", "cpt_schedule"]
+UNITS = ["cpt_megakernel", "cpt_wavefront", "cpt_query", "cpt_display", "cpt_schedule", "cpt_reproject"]
 FLAGS = [f for f in _build.HIPCC_FLAGS if f != "-shared"] + ["--cuda-device-only", "-S"]
 META = [".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
         ".group_segment_fixed_size"]
@@ -83,13 +89,37 @@ def parse(path):
     return {k: (streams.get(k, []), meta.get(k, {})) for k in kernels}
 
 
+SOURCE_DIRS = ["cpppathtracer_amd/csrc", "include"]
+
+
+def tree_ids(rev=None):
+    """The git tree ids of SOURCE_DIRS at `rev`, or (None) of the working tree's files as a commit of
+    them would record them: what `git rev-parse COMMIT:DIR` prints for that commit, so a log made
+    before the commit can be tied to it."""
+    if rev:
+        return [sh("git", "-C", REPO, "rev-parse", "%s:%s" % (rev, d)).strip() for d in SOURCE_DIRS]
+    with tempfile.TemporaryDirectory() as tmp:
+        env = dict(os.environ, GIT_INDEX_FILE=os.path.join(tmp, "index"))
+        sh("git", "-C", REPO, "read-tree", "HEAD", env=env)
+        sh("git", "-C", REPO, "add", "-A", "--", *SOURCE_DIRS, env=env)
+        return [sh("git", "-C", REPO, "write-tree", "--prefix=%s/" % d, env=env).strip() for d in SOURCE_DIRS]
+
+
 def main():
-    rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
+    args = sys.argv[1:]
+    renames = {}
+    while "--rename" in args:
+        i = args.index("--rename")
+        old, new = args[i + 1].split("=", 1)
+        renames[new.strip()] = old.strip()
+        del args[i:i + 2]
+    rev = args[0] if args else "HEAD"
     parent = sh("git", "-C", REPO, "rev-parse", rev).strip()
     head = sh("git", "-C", REPO, "rev-parse", "HEAD").strip()
     dirty = bool(sh("git", "-C", REPO, "status", "--porcelain", "--", "cpppathtracer_amd/csrc", "include").strip())
-    print("# parent: %s" % parent)
-    print("# new:    %s%s" % (head, " + the working tree's uncommitted changes" if dirty else ""))
+    sources = lambda ids: ", ".join("%s %s" % (d, i) for d, i in zip(SOURCE_DIRS, ids))
+    print("# parent: %s (trees: %s)" % (parent, sources(tree_ids(parent))))
+    print("# new:    %s (trees: %s)" % ("the working tree, not yet a commit" if dirty else head, sources(tree_ids())))
     print("# %s" % " | ".join(sh(_build._hipcc(), "--version").splitlines()[:2]))
     print("# flags:  %s" % " ".join(FLAGS))
     bad = 0
@@ -97,7 +127,7 @@ def main():
         a_dir, b_dir, src = (os.path.join(tmp, d) for d in ("parent", "new", "src"))
         for d in (a_dir, b_dir, src):
             os.mkdir(d)
-        tar = subprocess.run(["git", "-C", REPO, "archive", parent, "cpppathtracer_amd/csrc", "include"], check=True,
+        tar = subprocess.run(["git", "-C", REPO, "archive", parent, *SOURCE_DIRS], check=True,
                              capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", src], input=tar, check=True)
         compile_units(src, a_dir)
@@ -107,6 +137,14 @@ def main():
         for unit in UNITS:
             a, b = parse(os.path.join(a_dir, unit + ".s")), parse(os.path.join(b_dir, unit + ".s"))
             names = demangle(sorted(set(a) | set(b)))
+            # a renamed kernel: the parent's entry moves under the new symbol, its own row goes
+            symbol = {v: k for k, v in names.items()}
+            for new, old in renames.items():
+                if new in symbol and old in symbol and symbol[old] in a:
+                    a[symbol[new]] = a.pop(symbol[old])
+                    names[symbol[new]] = "%s (parent: %s)" % (new, old)
+                    if symbol[old] not in b:
+                        del names[symbol[old]]
             print("## " + unit)
             for k in sorted(names, key=names.get):
                 sa, ma = a.get(k, ([], {}))
