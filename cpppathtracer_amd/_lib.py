@@ -105,6 +105,14 @@ PROTOTYPES = {
     "cpt_read_display_count": (_I, [_P, _P, _SZ]),
     "cpt_reproject_display": (_I, [_P, _P, _P, _I, ctypes.c_float, _U32]),
     "cpt_reproject_display_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_float, _P, _P]),
+    "cpt_history_capture": (_I, [_P, _P, _U32]),
+    "cpt_history_info": (_I, [_P, _P, _P]),
+    "cpt_reproject_accum_tracked": (_I, [_P, _P, _I, ctypes.c_float, _U32]),
+    "cpt_reproject_display_tracked": (_I, [_P, _P, _I, ctypes.c_float, _U32]),
+    "cpt_object_motion_host": (_I, [_P, _P, _I, _P]),
+    "cpt_reproject_tracked_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P]),
+    "cpt_reproject_display_tracked_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float,
+                                                _P, _P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1

@@ -590,7 +590,7 @@ void PathTracer::PipelineLoop() {
     }
 }
 
-bool PathTracer::SetDisplayReprojection(bool on, int max_history, float plane_tol) {
+bool PathTracer::SetDisplayReprojection(bool on, int max_history, float plane_tol, bool through_edits) {
     std::lock_guard<std::mutex> lk(mu_);
     // what cpt_reproject_display would refuse at every Refresh is refused here, once
     if (max_history < 1 || !(plane_tol >= 0.f) || !(plane_tol - plane_tol == 0.f)) {
@@ -599,6 +599,8 @@ bool PathTracer::SetDisplayReprojection(bool on, int max_history, float plane_to
         return false;
     }
     display_reproject_ = on;
+    display_through_edits_ = on && through_edits;
+    loop_history_ = false;   // whatever history the context holds is not this loop's
     display_max_history_ = max_history;
     display_plane_tol_ = plane_tol;
     prev_pass_ = false;   // the first pass after a switch restarts
@@ -614,18 +616,74 @@ bool PathTracer::SetDisplayReprojection(bool on, int max_history, float plane_to
 bool PathTracer::DisplayPassWithHistory(MotionalCamera& cma) {
     const bool had_prev = prev_pass_, refreshed = cma.cur_sample_idx_ == 1;
     prev_pass_ = false;
+    const uint32_t walk = ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u;
+    // (a frame under 16 pixels either way has no launch region: no display pass ever ran there)
+    auto prev_fits = [&] {
+        return had_prev && prev_cam_.width_ == width_ && prev_cam_.height_ == height_ && width_ >= 16 && height_ >= 16 && !frame_;
+    };
+    // through_edits.  The context's captured history serves this loop only while it is the previous
+    // pass's: captured or renewed by this loop (loop_history_; Reproject, CaptureHistory,
+    // ReprojectTracked and SetDisplayReprojection clear it, the untracked C calls drop the capture
+    // itself), at the scene revision of the previous pass, and at a camera that equals prev_cam_ in
+    // every field but the sample index.  Anything else is not trusted: the history is captured anew
+    // at the previous pass's camera where the context still holds that pass's scene, and the display
+    // restarts where it does not.
+    if (!had_prev) loop_history_ = false;
+    auto history_is_prev = [&](cpt_ctx* ctx, bool& is_prev) {
+        int valid = 0;
+        cpt_camera cam;
+        is_prev = false;
+        if (cpt_history_info(ctx, &valid, &cam) != CPT_OK) return false;
+        if (valid && loop_history_ && loop_history_rev_ == prev_scene_rev_) {
+            cpt_camera prev = *reinterpret_cast<const cpt_camera*>(&prev_cam_);
+            prev.cur_sample_idx = cam.cur_sample_idx;
+            is_prev = std::memcmp(&prev, &cam, sizeof(cam)) == 0;
+        }
+        return true;
+    };
+    // A move or an edit is about to reach the context: capture before SyncScene lets it.  (Revision()
+    // is read before SyncScene reads it again: an UpdateObject from another thread that lands
+    // between the two is not seen here, no capture is made for it, and the pass below then finds an
+    // edited scene without a history of the previous pass and restarts the display.  Safe, but a
+    // restart that through_edits would otherwise have avoided.)
+    if (display_through_edits_ && prev_fits() && !tiles_.empty() && tiles_[0].scene_synced &&
+        (refreshed || SceneBVH::Revision() != tiles_[0].scene_rev || tiles_[0].scene_rev != prev_scene_rev_)) {
+        cpt_ctx* ctx = tiles_[0].ctx;
+        bool is_prev = false;
+        if (!history_is_prev(ctx, is_prev)) return Fail("cpt_history_info", ctx);
+        if (!is_prev) {
+            loop_history_ = false;
+            // (edits another call already brought to the context cannot be captured behind)
+            if (tiles_[0].scene_build == prev_scene_build_ && tiles_[0].scene_rev == prev_scene_rev_) {
+                if (cpt_history_capture(ctx, reinterpret_cast<const cpt_camera*>(&prev_cam_), walk) != CPT_OK)
+                    return Fail("cpt_history_capture", ctx);
+                loop_history_ = true;
+                loop_history_rev_ = prev_scene_rev_;
+            }
+        }
+    }
     if (!SyncScene() || !EnsureFrame(cma)) return false;
-    if (refreshed) {
-        const Tile& t0 = tiles_[0];
-        // (a frame under 16 pixels either way has no launch region: no display pass ever ran there)
-        const bool carry = had_prev && prev_cam_.width_ == width_ && prev_cam_.height_ == height_ && width_ >= 16 &&
-                           height_ >= 16 && t0.scene_build == prev_scene_build_ && t0.scene_rev == prev_scene_rev_ && !frame_;
-        if (carry) {
+    const Tile& t0 = tiles_[0];
+    const bool same_build = t0.scene_build == prev_scene_build_, same_rev = t0.scene_rev == prev_scene_rev_;
+    const bool edited = display_through_edits_ && had_prev && same_build && !same_rev;
+    if (refreshed || edited) {
+        bool carry = prev_fits() && same_build && (same_rev || display_through_edits_);
+        if (carry && display_through_edits_) {
+            // dropped by a new frame or scene, never captured, or not the previous pass's: restart
+            if (!history_is_prev(t0.ctx, carry)) return Fail("cpt_history_info", t0.ctx);
+        }
+        if (carry && display_through_edits_) {
+            if (cpt_reproject_display_tracked(t0.ctx, reinterpret_cast<const cpt_camera*>(&cma), display_max_history_,
+                                              display_plane_tol_, walk) != CPT_OK)
+                return Fail("cpt_reproject_display_tracked", t0.ctx);
+            loop_history_rev_ = t0.scene_rev;   // the call renewed the history: cma, the current objects
+        } else if (carry) {
             if (cpt_reproject_display(t0.ctx, reinterpret_cast<const cpt_camera*>(&prev_cam_), reinterpret_cast<const cpt_camera*>(&cma),
-                                      display_max_history_, display_plane_tol_, ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK)
+                                      display_max_history_, display_plane_tol_, walk) != CPT_OK)
                 return Fail("cpt_reproject_display", t0.ctx);
-        } else if (cpt_reset_display(FrameCtx()) != CPT_OK) {
-            return Fail("cpt_reset_display");
+        } else {
+            loop_history_ = false;
+            if (cpt_reset_display(FrameCtx()) != CPT_OK) return Fail("cpt_reset_display");
         }
     }
     if (!RenderPass(cma, 1, false)) return false;
@@ -906,6 +964,48 @@ bool PathTracer::Reproject(const MotionalCamera& from, int max_history, float pl
                             plane_tol, ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK ||
         cpt_synchronize(ctx) != CPT_OK)
         return Fail("cpt_reproject_accum", ctx);
+    loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
+    return true;
+}
+
+bool PathTracer::CaptureHistory() {
+    if (!camera_) {
+        err_ = "CaptureHistory: SetCamera first";
+        return false;
+    }
+    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
+    const MotionalCamera cam = query_camera(*camera_);
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!SyncScene() || !EnsureFrame(cam)) return false;
+    if (frame_) {
+        err_ = "CaptureHistory: not available with SetDevices(n > 1), the row tiles own their accumulators";
+        return false;
+    }
+    cpt_ctx* ctx = tiles_[0].ctx;
+    if (cpt_history_capture(ctx, reinterpret_cast<const cpt_camera*>(&cam), ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK)
+        return Fail("cpt_history_capture", ctx);
+    loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
+    return true;
+}
+
+bool PathTracer::ReprojectTracked(int max_history, float plane_tol) {
+    if (!camera_) {
+        err_ = "ReprojectTracked: SetCamera first";
+        return false;
+    }
+    const MotionalCamera to = query_camera(*camera_);
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!SyncScene() || !EnsureFrame(to)) return false;   // the pending UpdateObjects are refit here
+    if (frame_) {
+        err_ = "ReprojectTracked: not available with SetDevices(n > 1), the row tiles own their accumulators";
+        return false;
+    }
+    cpt_ctx* ctx = tiles_[0].ctx;
+    if (cpt_reproject_accum_tracked(ctx, reinterpret_cast<const cpt_camera*>(&to), max_history, plane_tol,
+                                    ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK ||
+        cpt_synchronize(ctx) != CPT_OK)
+        return Fail("cpt_reproject_accum_tracked", ctx);
+    loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
     return true;
 }
 

@@ -241,7 +241,9 @@ int cpt_set_frame(cpt_ctx* c, int width, int height, const int32_t* rows, int n_
     }
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream()));
-    c->frame = Frame{};   // releases everything the previous frame held
+    // releases everything the previous frame held; with it goes the captured history of the tracked
+    // reprojection (ReprojectState: planes of the old size, the motion table and its events)
+    c->frame = Frame{};
     Frame& f = c->frame;
     static std::atomic<uint64_t> frame_gens{0};
     c->frame_gen = ++frame_gens;

@@ -1,11 +1,14 @@
 // cpt_capi_reproject.cpp — the C-ABI's reprojection of the accumulated frame (include/cpt.h,
 // cpt_reproject_accum) and of the display state (§22: cpt_reproject_display) to a
-// moved camera, their timing, and the host-only entries on the same arithmetic.  The G-buffers
+// moved camera, the tracked variants that keep the history's G-buffer and follow object edits
+// (§23: cpt_history_capture, cpt_reproject_accum_tracked, cpt_reproject_display_tracked), their
+// timing, and the host-only entries on the same arithmetic.  The G-buffers
 // are cpt_query.hip's kernel, the look-ups cpt_reproject.hip's; the arithmetic is
 // cpt_reproject.hpp's on both sides.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <new>
 #include <utility>
 
 #include "cpt_context.hpp"
@@ -61,6 +64,8 @@ int ensure_planes(cpt_ctx* c) {
 int trace_pair(cpt_ctx* c, const cpt::KParams& p0, const cpt::KParams& p1, hipStream_t s) {
     GBufferState& g = c->frame.gbuffer;
     ReprojectState& r = c->frame.reproject;
+    // the trace at `from` overwrites the planes a captured history lives in: it is gone
+    r.captured = false;
     HIP_TRY(c, hipEventRecord(c->t_reproject.t0, s));
     HIP_TRY(c, cpt::launch_ray_query(p0, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
                                      cpt::QueryOut{r.d_id, r.d_t, g.d_normal, nullptr}, s));
@@ -70,6 +75,71 @@ int trace_pair(cpt_ctx* c, const cpt::KParams& p0, const cpt::KParams& p1, hipSt
     g.valid = true;
     HIP_TRY(c, hipEventRecord(c->ev_reproject[1], s));
     return CPT_OK;
+}
+
+// The tracked calls' one trace, with the same timing events: none at the captured camera (ms3[0]
+// reads 0), then the G-buffer at `to` into the frame's own.
+int trace_to(cpt_ctx* c, const cpt::KParams& p1, hipStream_t s) {
+    GBufferState& g = c->frame.gbuffer;
+    HIP_TRY(c, hipEventRecord(c->t_reproject.t0, s));
+    HIP_TRY(c, hipEventRecord(c->ev_reproject[0], s));
+    HIP_TRY(c, cpt::launch_ray_query(p1, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
+                                     cpt::QueryOut{g.d_id, g.d_t, g.d_normal, g.d_albedo}, s));
+    g.valid = true;
+    HIP_TRY(c, hipEventRecord(c->ev_reproject[1], s));
+    return CPT_OK;
+}
+
+// What the tracked calls ask beyond `checked`, and the planes they need beyond ensure_planes.
+int tracked_ready(cpt_ctx* c, const char* who) {
+    ReprojectState& r = c->frame.reproject;
+    if (!r.captured) return fail(c, CPT_ERR_STATE, "%s: no captured history (cpt_history_capture first)", who);
+    int rc;
+    if ((rc = ensure_planes(c)) != CPT_OK || (rc = r.d_id_next.ensure(c, c->npix())) != CPT_OK ||
+        (rc = r.d_t_next.ensure(c, c->npix())) != CPT_OK)
+        return rc;
+    return CPT_OK;
+}
+
+// The motion table of the objects since the capture, uploaded on the stream; *table stays nullptr
+// when no object was edited (nothing is derived or uploaded then).
+int motion_table(cpt_ctx* c, hipStream_t s, const cpt_object_motion** table) {
+    ReprojectState& r = c->frame.reproject;
+    *table = nullptr;
+    const size_t n = c->objs.size();
+    if (r.objs.size() != n) return fail(c, CPT_ERR_STATE, "the captured history holds %zu objects, the scene %zu", r.objs.size(), n);
+    bool edited = false;
+    for (size_t k = 0; k < n && !edited; ++k)
+        edited = !rp::same_geometry(r.objs[k], c->objs[k]) || !rp::same_material(r.objs[k].material, c->objs[k].material);
+    if (!edited) return CPT_OK;
+    // two host tables by turns: an upload reads its table until its event, so this call waits only
+    // for the upload of the call before the last, which has long retired unless three edited calls
+    // are queued behind one unfinished render
+    const int b = r.motion_turn ^= 1;
+    if (!r.ev_motion[b]) HIP_TRY(c, r.ev_motion[b].create(hipEventDisableTiming));
+    else HIP_TRY(c, hipEventSynchronize(r.ev_motion[b]));
+    std::vector<cpt_object_motion>& h = r.motion_h[b];
+    try {
+        h.resize(n);
+    } catch (const std::bad_alloc&) {
+        return fail(c, CPT_ERR_OUT_OF_MEMORY, "motion table: host allocation failed");
+    }
+    for (size_t k = 0; k < n; ++k) h[k] = rp::motion_of(r.objs[k], c->objs[k]);
+    if (int rc = r.d_motion.ensure(c, n)) return rc;
+    HIP_TRY(c, hipMemcpyAsync(r.d_motion, h.data(), n * sizeof(cpt_object_motion), hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipEventRecord(r.ev_motion[b], s));
+    *table = r.d_motion;
+    return CPT_OK;
+}
+
+// Behind a tracked look-up: `to`, its id and distance planes (the kernel wrote them to the second
+// planes) and the current objects are the captured history.
+void renew_history(cpt_ctx* c, const cpt_camera* to, bool edited) {
+    ReprojectState& r = c->frame.reproject;
+    std::swap(r.d_id, r.d_id_next);
+    std::swap(r.d_t, r.d_t_next);
+    r.cam = *to;
+    if (edited) r.objs = c->objs;   // same size: assigns in place
 }
 
 }  // namespace
@@ -110,6 +180,7 @@ int cpt_reproject_accum(cpt_ctx* c, const cpt_camera* from, const cpt_camera* to
     HIP_TRY(c, cpt::launch_reproject(a, s));
     HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
     c->t_reproject.recorded = true;
+    c->reproject_tracked = false;
     // the second plane is the accumulator from here on: work already queued holds the old pointer
     // by value and runs before the kernel; every later call reads the member
     std::swap(f.d_accum, r.d_accum);
@@ -164,6 +235,7 @@ int cpt_reproject_display(cpt_ctx* c, const cpt_camera* from, const cpt_camera* 
     HIP_TRY(c, cpt::launch_reproject_display(a, s));
     HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
     c->t_reproject.recorded = true;
+    c->reproject_tracked = false;
     // the second planes are the display state from here on (as the accumulator's above); the
     // kernel wrote every pixel of the frame, so they need no clearing
     std::swap(d.d_mix, d.d_mix_next);
@@ -171,9 +243,149 @@ int cpt_reproject_display(cpt_ctx* c, const cpt_camera* from, const cpt_camera* 
     return CPT_OK;
 }
 
+int cpt_history_capture(cpt_ctx* c, const cpt_camera* cam, uint32_t flags) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    if (int rc = checked(c, "cpt_history_capture", cam, cam, 1, 0.f, flags)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    GBufferState& g = c->frame.gbuffer;
+    ReprojectState& r = c->frame.reproject;
+    if (int rc = ensure_planes(c)) return rc;
+    // (from here on an earlier capture is gone, also if a launch below fails: a failed capture
+    // leaves no history, not the previous one)
+    try {
+        r.objs = c->objs;
+    } catch (const std::bad_alloc&) {
+        return fail(c, CPT_ERR_OUT_OF_MEMORY, "cpt_history_capture: host allocation failed");
+    }
+    r.captured = false;   // until the planes are queued
+    cpt::KParams p;
+    fill_params(c, cam, 0, 0, flags, p);
+    hipStream_t s = c->stream();
+    // the whole G-buffer at cam into the frame's own (the kernel writes all four planes), then its
+    // id and distance into the history's
+    HIP_TRY(c, cpt::launch_ray_query(p, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
+                                     cpt::QueryOut{g.d_id, g.d_t, g.d_normal, g.d_albedo}, s));
+    g.valid = true;
+    HIP_TRY(c, hipMemcpyAsync(r.d_id, g.d_id, c->npix() * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(r.d_t, g.d_t, c->npix() * sizeof(float), hipMemcpyDeviceToDevice, s));
+    r.cam = *cam;
+    r.captured = true;
+    return CPT_OK;
+}
+
+int cpt_history_info(cpt_ctx* c, int* valid, cpt_camera* cam) {
+    if (!c || !valid) return CPT_ERR_INVALID_ARG;
+    const ReprojectState& r = c->frame.reproject;
+    *valid = r.captured ? 1 : 0;
+    if (cam && r.captured) *cam = r.cam;
+    return CPT_OK;
+}
+
+int cpt_reproject_accum_tracked(cpt_ctx* c, const cpt_camera* to, int max_history, float plane_tol, uint32_t flags) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    const char* who = "cpt_reproject_accum_tracked";
+    if (int rc = checked(c, who, to, to, max_history, plane_tol, flags)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    Frame& f = c->frame;
+    GBufferState& g = f.gbuffer;
+    ReprojectState& r = f.reproject;
+    int rc;
+    if ((rc = tracked_ready(c, who)) != CPT_OK || (rc = r.d_accum.ensure(c, c->npix())) != CPT_OK) return rc;
+    cpt::KParams p0, p1;
+    fill_params(c, &r.cam, 0, 0, flags, p0);
+    fill_params(c, to, 0, 0, flags, p1);
+    cpt::ReprojectTrackedArgs ta;
+    std::memset(&ta, 0, sizeof(ta));
+    cpt::ReprojectArgs& a = ta.look;
+    a.cam0 = p0.cam;
+    a.cam1 = p1.cam;
+    a.view0 = rp::old_view(r.cam);
+    a.width = c->width;
+    a.height = c->height;
+    a.id0 = r.d_id;
+    a.t0 = r.d_t;
+    a.id1 = g.d_id;
+    a.t1 = g.d_t;
+    a.normal1 = g.d_normal;
+    a.in = f.d_accum;
+    a.out = r.d_accum;
+    a.max_history = (float)max_history;
+    a.plane_tol = plane_tol;
+    ta.id_next = r.d_id_next;
+    ta.t_next = r.d_t_next;
+    hipStream_t s = c->stream();
+    if ((rc = motion_table(c, s, &ta.motion)) != CPT_OK || (rc = trace_to(c, p1, s)) != CPT_OK) return rc;
+    HIP_TRY(c, cpt::launch_reproject_tracked(ta, s));
+    HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
+    c->t_reproject.recorded = true;
+    c->reproject_tracked = true;
+    std::swap(f.d_accum, r.d_accum);   // as cpt_reproject_accum
+    f.adaptive.done = false;
+    renew_history(c, to, ta.motion != nullptr);
+    return CPT_OK;
+}
+
+int cpt_reproject_display_tracked(cpt_ctx* c, const cpt_camera* to, int max_history, float plane_tol, uint32_t flags) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    const char* who = "cpt_reproject_display_tracked";
+    if (int rc = checked(c, who, to, to, max_history, plane_tol, flags)) return rc;
+    Frame& f = c->frame;
+    DisplayBand& d = f.display;
+    const int w_eff = 16 * (c->width / 16), h_eff = 16 * (c->height / 16);
+    if (!d.d_mix) return fail(c, CPT_ERR_STATE, "%s: no display pass yet", who);
+    if (d.y0 != 0 || d.y1 != h_eff)
+        return fail(c, CPT_ERR_STATE, "%s: the display holds the band [%d, %d), not the full frame", who, d.y0, d.y1);
+    HIP_TRY(c, hipSetDevice(c->device));
+    GBufferState& g = f.gbuffer;
+    ReprojectState& r = f.reproject;
+    const size_t npix = c->npix();
+    int rc;
+    if ((rc = tracked_ready(c, who)) != CPT_OK || (rc = d.d_mix_next.ensure(c, 3 * npix)) != CPT_OK ||
+        (rc = d.d_count_next.ensure(c, npix)) != CPT_OK)
+        return rc;
+    cpt::KParams p0, p1;
+    fill_params(c, &r.cam, 0, 0, flags, p0);
+    fill_params(c, to, 0, 0, flags, p1);
+    cpt::ReprojectDisplayTrackedArgs ta;
+    std::memset(&ta, 0, sizeof(ta));
+    cpt::ReprojectDisplayArgs& a = ta.look;
+    a.cam0 = p0.cam;
+    a.cam1 = p1.cam;
+    a.view0 = rp::old_view(r.cam);
+    a.width = c->width;
+    a.height = c->height;
+    a.w_eff = w_eff;
+    a.h_eff = h_eff;
+    a.id0 = r.d_id;
+    a.t0 = r.d_t;
+    a.id1 = g.d_id;
+    a.t1 = g.d_t;
+    a.normal1 = g.d_normal;
+    a.mean_in = d.d_mix;
+    a.count_in = d.d_count;
+    a.mean_out = d.d_mix_next;
+    a.count_out = d.d_count_next;
+    a.max_history = (float)max_history;
+    a.plane_tol = plane_tol;
+    ta.id_next = r.d_id_next;
+    ta.t_next = r.d_t_next;
+    hipStream_t s = c->stream();
+    if ((rc = d.fill_count(c)) != CPT_OK || (rc = motion_table(c, s, &ta.motion)) != CPT_OK ||
+        (rc = trace_to(c, p1, s)) != CPT_OK)
+        return rc;
+    HIP_TRY(c, cpt::launch_reproject_display_tracked(ta, s));
+    HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
+    c->t_reproject.recorded = true;
+    c->reproject_tracked = true;
+    std::swap(d.d_mix, d.d_mix_next);   // as cpt_reproject_display
+    std::swap(d.d_count, d.d_count_next);
+    renew_history(c, to, ta.motion != nullptr);
+    return CPT_OK;
+}
+
 int cpt_last_reproject_ms(cpt_ctx* c, float* ms) {
     if (!c || !ms) return CPT_ERR_INVALID_ARG;
-    if (!c->t_reproject.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_reproject_ms: no cpt_reproject_accum or cpt_reproject_display yet");
+    if (!c->t_reproject.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_reproject_ms: no reprojection call (cpt_reproject_accum, _display or their tracked variants) yet");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipEventSynchronize(c->t_reproject.t1));
     HIP_TRY(c, hipEventElapsedTime(ms, c->t_reproject.t0, c->t_reproject.t1));
@@ -182,11 +394,12 @@ int cpt_last_reproject_ms(cpt_ctx* c, float* ms) {
 
 int cpt_last_reproject_launch_ms(cpt_ctx* c, float* ms3) {
     if (!c || !ms3) return CPT_ERR_INVALID_ARG;
-    if (!c->t_reproject.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_reproject_launch_ms: no cpt_reproject_accum or cpt_reproject_display yet");
+    if (!c->t_reproject.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_reproject_launch_ms: no reprojection call (cpt_reproject_accum, _display or their tracked variants) yet");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipEventSynchronize(c->t_reproject.t1));
     const hipEvent_t ev[4] = {c->t_reproject.t0, c->ev_reproject[0], c->ev_reproject[1], c->t_reproject.t1};
     for (int k = 0; k < 3; ++k) HIP_TRY(c, hipEventElapsedTime(ms3 + k, ev[k], ev[k + 1]));
+    if (c->reproject_tracked) ms3[0] = 0.f;   // no trace ran between the first two events
     return CPT_OK;
 }
 
@@ -228,6 +441,73 @@ int cpt_reproject_display_host(const cpt_camera* cam0, const cpt_camera* cam1, i
             const rp::Px r = rp::display_pixel(src, v, o1, width, height, w_eff, h_eff, x, y, id1[i], t1[i],
                                                rp::V3{normal1[3 * i], normal1[3 * i + 1], normal1[3 * i + 2]},
                                                rp::V3{dir1[3 * i], dir1[3 * i + 1], dir1[3 * i + 2]}, (float)max_history, plane_tol);
+            mean_out[3 * i] = r.r;
+            mean_out[3 * i + 1] = r.g;
+            mean_out[3 * i + 2] = r.b;
+            count_out[i] = r.n;
+        }
+    return CPT_OK;
+}
+
+int cpt_object_motion_host(const cpt_object* old_objs, const cpt_object* new_objs, int n, cpt_object_motion* out_table) {
+    if (n < 0 || (n > 0 && (!old_objs || !new_objs || !out_table))) return CPT_ERR_INVALID_ARG;
+    for (int k = 0; k < n; ++k) out_table[k] = rp::motion_of(old_objs[k], new_objs[k]);
+    return CPT_OK;
+}
+
+// the tracked host entries' table: NULL with 0 records, or every hit's id inside it
+static bool table_ok(const cpt_object_motion* table, int n_objs, const int32_t* id1, size_t npix) {
+    if (!table) return n_objs == 0;
+    if (n_objs <= 0) return false;
+    for (size_t i = 0; i < npix; ++i)
+        if (id1[i] >= n_objs) return false;
+    return true;
+}
+
+int cpt_reproject_tracked_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0,
+                               const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
+                               const float* normal1, const float* accum_in, const cpt_object_motion* table, int n_objs,
+                               int max_history, float plane_tol, float* accum_out) {
+    if (!cam0 || !cam1 || width <= 0 || height <= 0 || !dir0 || !dir1 || !id0 || !t0 || !id1 || !t1 || !normal1 || !accum_in ||
+        !accum_out || accum_in == accum_out || !args_ok(max_history, plane_tol))
+        return CPT_ERR_INVALID_ARG;
+    for (const cpt_camera* cam : {cam0, cam1})
+        if (cam->width != width || cam->height != height) return CPT_ERR_INVALID_ARG;
+    const size_t npix = (size_t)width * height;
+    if (!table_ok(table, n_objs, id1, npix)) return CPT_ERR_INVALID_ARG;
+    const rp::OldView v = rp::old_view(*cam0);
+    const rp::V3 o1 = rp::v3_of(cam1->origin);
+    const rp::PlaneSrc src{reinterpret_cast<const rp::Px*>(accum_in), id0, t0, dir0};
+    rp::Px* out = reinterpret_cast<rp::Px*>(accum_out);
+    for (size_t i = 0; i < npix; ++i)
+        out[i] = rp::pixel<false, rp::PlaneSrc, rp::TableMotion>(
+            src, v, o1, width, height, id1[i], t1[i], rp::V3{normal1[3 * i], normal1[3 * i + 1], normal1[3 * i + 2]},
+            rp::V3{dir1[3 * i], dir1[3 * i + 1], dir1[3 * i + 2]}, (float)max_history, plane_tol, 0, 0, rp::TableMotion{table});
+    return CPT_OK;
+}
+
+int cpt_reproject_display_tracked_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height,
+                                       const float* dir0, const float* dir1, const int32_t* id0, const float* t0,
+                                       const int32_t* id1, const float* t1, const float* normal1, const float* mean_in,
+                                       const float* count_in, const cpt_object_motion* table, int n_objs, int max_history,
+                                       float plane_tol, float* mean_out, float* count_out) {
+    if (!cam0 || !cam1 || width <= 0 || height <= 0 || !dir0 || !dir1 || !id0 || !t0 || !id1 || !t1 || !normal1 || !mean_in ||
+        !count_in || !mean_out || !count_out || mean_in == mean_out || count_in == count_out || !args_ok(max_history, plane_tol))
+        return CPT_ERR_INVALID_ARG;
+    for (const cpt_camera* cam : {cam0, cam1})
+        if (cam->width != width || cam->height != height) return CPT_ERR_INVALID_ARG;
+    if (!table_ok(table, n_objs, id1, (size_t)width * height)) return CPT_ERR_INVALID_ARG;
+    const rp::OldView v = rp::old_view(*cam0);
+    const rp::V3 o1 = rp::v3_of(cam1->origin);
+    const rp::DisplayPlaneSrc src{mean_in, count_in, id0, t0, dir0};
+    const int w_eff = 16 * (width / 16), h_eff = 16 * (height / 16);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const size_t i = (size_t)y * width + x;
+            const rp::Px r = rp::display_pixel(src, v, o1, width, height, w_eff, h_eff, x, y, id1[i], t1[i],
+                                               rp::V3{normal1[3 * i], normal1[3 * i + 1], normal1[3 * i + 2]},
+                                               rp::V3{dir1[3 * i], dir1[3 * i + 1], dir1[3 * i + 2]}, (float)max_history, plane_tol,
+                                               rp::TableMotion{table});
             mean_out[3 * i] = r.r;
             mean_out[3 * i + 1] = r.g;
             mean_out[3 * i + 2] = r.b;

@@ -154,6 +154,24 @@ struct ReprojectState {
     DevBuf<int32_t> d_id;      // the G-buffer at the camera the history was rendered with: object
     DevBuf<float> d_t;         // index and hit distance per pixel
     DevBuf<float4> d_accum;    // the plane the next call writes; swapped with Frame::d_accum behind it
+    // The captured history (cpt_history_capture and the tracked calls): d_id / d_t
+    // then hold the G-buffer at `cam` of the scene as `objs` had it.  Dropped by the untracked
+    // cpt_reproject_accum / cpt_reproject_display (they trace `from` into d_id / d_t), by cpt_set_scene
+    // (object indices change their meaning) and, with everything else here, by cpt_set_frame, which
+    // assigns a fresh Frame: the planes have the old frame's size.
+    bool captured = false;
+    cpt_camera cam{};
+    std::vector<cpt_object> objs;
+    // the planes a tracked look-up writes the new frame's id and distance to; swapped with d_id /
+    // d_t behind it
+    DevBuf<int32_t> d_id_next;
+    DevBuf<float> d_t_next;
+    // the motion table of the last tracked call after an edit: the host's copies, used by turns,
+    // each read by its upload on the stream until its event, and the device's
+    std::vector<cpt_object_motion> motion_h[2];
+    DevBuf<cpt_object_motion> d_motion;
+    DevEvent ev_motion[2];
+    int motion_turn = 0;
 };
 
 struct Frame {
@@ -195,6 +213,7 @@ struct cpt_ctx {
     TimedSpan t_query;     // the last query kernel (cpt_gbuffer, cpt_trace_rays, cpt_pick)
     TimedSpan t_reproject; // the last cpt_reproject_accum's or cpt_reproject_display's launches ...
     DevEvent ev_reproject[2];   // ... and the two points between them: after each G-buffer trace
+    bool reproject_tracked = false;   // ... of a tracked call: the trace at `from` did not run
     std::string err;
 
     // scene

@@ -1,6 +1,7 @@
 // cpt_reproject.hpp — reprojection of the accumulated frame and of the display's
 // running mean with its per-pixel sample counts (§22) to a moved camera, shared by the device
-// (cpt_reproject.hip) and the host (cpt_reproject_host, cpt_reproject_display_host).
+// (cpt_reproject.hip) and the host (cpt_reproject_host, cpt_reproject_display_host); and the tracked
+// variants of both (§23), which follow edited objects back to where the history saw them.
 //
 // Backward reprojection: the new pixel's first hit (or, for the sky, its direction as a point at
 // infinity) is projected into the camera the history was rendered with, and the four accumulator
@@ -17,6 +18,8 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <cstring>
 
 #include "../../include/cpt.h"
 #include "cpt_internal.hpp"
@@ -105,6 +108,88 @@ __host__ __device__ inline float snap(float f) {
     return d <= SNAP ? r : f;
 }
 
+// Tracked reprojection: where an object stood when the history was captured.  One
+// record per object index, derived on the host from the object as captured (0) and as it is now (1)
+// and read by the look-up as a plain table.  Every kind is an axis-aligned scaling plus a
+// translation, so the hit's normal is the same on both sides.
+//   SAME      geometry and material fields bytewise equal: the point is not touched
+//   SPHERE    c0 + (P - c1) * (r0 / r1)
+//   CYLINDER  x, z: c0 + (P - c1) * (r0 / r1); y: c0.y + (P.y - c1.y) * (h0 / h1)
+//   PLATFORM  (P.x, y_pos0, P.z)
+//   DROP      no history: another primitive type, a changed material (its radiance is stale), a
+//             divisor that is not finite or <= 0, a scale that is not finite
+// Field by field, bytewise (-0 is not 0, a NaN equals itself); the structs' padding is not data.
+inline bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; }
+
+inline bool same_material(const cpt_material& a, const cpt_material& b) {
+    if (a.type != b.type || (a.have_tex != 0) != (b.have_tex != 0)) return false;
+    if (a.have_tex ? a.u.tex != b.u.tex
+                   : !(same_bits(a.u.kd.x, b.u.kd.x) && same_bits(a.u.kd.y, b.u.kd.y) && same_bits(a.u.kd.z, b.u.kd.z)))
+        return false;
+    return same_bits(a.refractive_index, b.refractive_index) && same_bits(a.emit_intensity, b.emit_intensity) &&
+           same_bits(a.smoothness, b.smoothness) && same_bits(a.reflectivity, b.reflectivity);
+}
+
+inline bool same_geometry(const cpt_object& a, const cpt_object& b) {
+    return a.type == b.type && same_bits(a.center.x, b.center.x) && same_bits(a.center.y, b.center.y) &&
+           same_bits(a.center.z, b.center.z) && same_bits(a.radius, b.radius) && same_bits(a.y_pos, b.y_pos) &&
+           same_bits(a.height, b.height);
+}
+
+inline cpt_object_motion motion_of(const cpt_object& o0, const cpt_object& o1) {
+#pragma clang fp contract(off)
+    cpt_object_motion m;
+    std::memset(&m, 0, sizeof(m));
+    m.c0 = o0.center;
+    m.c1 = o1.center;
+    m.s_xz = m.s_y = 1.0f;
+    const bool same_mat = same_material(o0.material, o1.material), same_geo = same_geometry(o0, o1);
+    m.kind = CPT_MOTION_DROP;
+    if (same_mat && same_geo) {
+        m.kind = CPT_MOTION_SAME;
+    } else if (same_mat && o0.type == o1.type) {
+        const bool r_ok = finite(o1.radius) && o1.radius > 0.0f, h_ok = finite(o1.height) && o1.height > 0.0f;
+        if (o1.type == CPT_PRIM_SPHERE && r_ok) {
+            m.s_xz = m.s_y = o0.radius / o1.radius;
+            if (finite(m.s_xz)) m.kind = CPT_MOTION_SPHERE;
+        } else if (o1.type == CPT_PRIM_CYLINDER && r_ok && h_ok) {
+            m.s_xz = o0.radius / o1.radius;
+            m.s_y = o0.height / o1.height;
+            if (finite(m.s_xz) && finite(m.s_y)) m.kind = CPT_MOTION_CYLINDER;
+        } else if (o1.type == CPT_PRIM_PLATFORM) {
+            m.c0.y = o0.y_pos;
+            m.c1.y = o1.y_pos;
+            m.kind = CPT_MOTION_PLATFORM;
+        }
+    }
+    return m;
+}
+
+// pixel's `motion` of the untracked look-ups: none, and no code.
+struct NoMotion {
+    static constexpr bool TRACKED = false;
+};
+
+// pixel's `motion` of the tracked look-ups: the table (nullptr: nothing was edited since the capture).
+struct TableMotion {
+    static constexpr bool TRACKED = true;
+    const cpt_object_motion* table;
+    // P, a point of object `id` now, becomes the point it was at the capture; false: no history
+    __host__ __device__ bool to_old(int32_t id, V3& P) const {
+#pragma clang fp contract(off)
+        if (!table) return true;
+        const cpt_object_motion m = table[id];
+        if (m.kind == CPT_MOTION_SAME) return true;
+        if (m.kind == CPT_MOTION_PLATFORM) {
+            P.y = m.c0.y;
+            return true;
+        }
+        if (m.kind != CPT_MOTION_SPHERE && m.kind != CPT_MOTION_CYLINDER) return false;
+        P = V3{m.c0.x + (P.x - m.c1.x) * m.s_xz, m.c0.y + (P.y - m.c1.y) * m.s_y, m.c0.z + (P.z - m.c1.z) * m.s_xz};
+        return true;
+    }
+};
+
 // A tap's history: the accumulator's pixel or, DISPLAY, the display state's.
 template <bool DISPLAY, typename Src>
 __host__ __device__ inline Px history(const Src& src, size_t k) {
@@ -121,14 +206,19 @@ __host__ __device__ inline Px history(const Src& src, size_t k) {
 // inside w_eff x h_eff count.  id1, t1, n1 and d1 are the new pixel's G-buffer entry and centre-ray
 // direction, o1 the new camera's origin.  One body and no wrapper on the accumulator's side: its
 // instantiation compiles to the kernel it was before the display look-up joined it (§22).
-template <bool DISPLAY = false, typename Src>
+// `motion` (§23): TableMotion maps the new hit point to the point its object held when the history
+// was captured, and that point stands for P in the projection and the plane test; NoMotion, the
+// default, adds no code: both untracked kernels compile to the instructions they were.
+template <bool DISPLAY = false, typename Src, typename Motion = NoMotion>
 __host__ __device__ inline Px pixel(const Src& src, const OldView& v, const V3& o1, int width, int height, int32_t id1,
                                     float t1, const V3& n1, const V3& d1, float max_history, float plane_tol, int w_eff = 0,
-                                    int h_eff = 0) {
+                                    int h_eff = 0, const Motion& motion = Motion{}) {
 #pragma clang fp contract(off)
     const Px none{0.0f, 0.0f, 0.0f, 0.0f};
     const bool hit = id1 >= 0;
-    const V3 P = at(o1, t1, d1);
+    V3 P = at(o1, t1, d1);
+    if constexpr (Motion::TRACKED)   // the hit point as its object held it at the capture (§23)
+        if (hit && !motion.to_old(id1, P)) return none;
     const V3 q = hit ? sub(P, v.o) : d1;
     float fx, fy;
     if (!project(v, q, fx, fy)) return none;
@@ -183,12 +273,12 @@ __host__ __device__ inline Px pixel(const Src& src, const OldView& v, const V3& 
 // One output pixel (x1, y1) of the display state (cpt_reproject_display): (the Mix
 // mean's rgb, the sample count).  The display's launch region is w_eff x h_eff: a pixel outside it
 // holds nothing, a tap outside it does not count; the mean is blended as it is, the count beside it.
-template <typename Src>
+template <typename Src, typename Motion = NoMotion>
 __host__ __device__ inline Px display_pixel(const Src& src, const OldView& v, const V3& o1, int width, int height, int w_eff,
                                             int h_eff, int x1, int y1, int32_t id1, float t1, const V3& n1, const V3& d1,
-                                            float max_history, float plane_tol) {
+                                            float max_history, float plane_tol, const Motion& motion = Motion{}) {
     if (x1 >= w_eff || y1 >= h_eff) return Px{0.0f, 0.0f, 0.0f, 0.0f};
-    return pixel<true>(src, v, o1, width, height, id1, t1, n1, d1, max_history, plane_tol, w_eff, h_eff);
+    return pixel<true, Src, Motion>(src, v, o1, width, height, id1, t1, n1, d1, max_history, plane_tol, w_eff, h_eff, motion);
 }
 
 // The old frame as plain arrays (the host entry).
@@ -256,5 +346,25 @@ struct ReprojectDisplayArgs {
     float max_history, plane_tol;
 };
 hipError_t launch_reproject_display(const ReprojectDisplayArgs& a, hipStream_t stream);
+
+// k_reproject_accum_tracked's and k_reproject_display_tracked's arguments: the
+// untracked kernel's, with id0 / t0 the captured history's planes and cam0 / view0 its camera; the
+// motion table (one record per object index; nullptr: no object was edited since the capture) and
+// the planes that take the new frame's id and distance, the next call's history (not id0 / t0).
+struct ReprojectTrackedArgs {
+    ReprojectArgs look;
+    const cpt_object_motion* motion;
+    int32_t* id_next;
+    float* t_next;
+};
+hipError_t launch_reproject_tracked(const ReprojectTrackedArgs& a, hipStream_t stream);
+
+struct ReprojectDisplayTrackedArgs {
+    ReprojectDisplayArgs look;
+    const cpt_object_motion* motion;
+    int32_t* id_next;
+    float* t_next;
+};
+hipError_t launch_reproject_display_tracked(const ReprojectDisplayTrackedArgs& a, hipStream_t stream);
 
 }  // namespace cpt

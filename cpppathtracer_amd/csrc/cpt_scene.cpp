@@ -314,6 +314,7 @@ extern "C" {
 int cpt_set_scene(cpt_ctx* c, const cpt_object* objs, int n) {
     if (!c || n < 0 || (n > 0 && !objs)) return c ? fail(c, CPT_ERR_INVALID_ARG, "cpt_set_scene: bad arguments") : CPT_ERR_INVALID_ARG;
     c->scene_set = false;   // until the new scene is uploaded
+    c->frame.reproject.captured = false;   // object indices mean other objects from here on
     try {
         c->objs.assign(objs, objs + n);
         build_host_bvh(c->bvh, c->objs);

@@ -16,7 +16,7 @@ from ._lib import (CPT_PATH_WAVEFRONT, CPT_RENDER_ACCUMULATE, CPT_RENDER_AUX, CP
 
 PATHS = ("megakernel", "wavefront")
 from .tiling import tile_grid
-from .types import CAMERA_DTYPE, OBJECT_DTYPE
+from .types import CAMERA_DTYPE, MOTION_DTYPE, OBJECT_DTYPE
 
 
 def _p(a):
@@ -73,6 +73,65 @@ def reproject_display_host(cam0, cam1, dir0, dir1, id0, t0, id1, t1, normal1, me
     mean_out, count_out = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.float32)
     check(L.cpt_reproject_display_host(_p(a), _p(b), W, H, _p(d0), _p(d1), _p(i0), _p(tt0), _p(i1), _p(tt1), _p(nn), _p(m), _p(c),
                                        int(max_history), ctypes.c_float(plane_tol), _p(mean_out), _p(count_out)))
+    return mean_out, count_out
+
+
+def object_motion_host(old_objs, new_objs):
+    """cpt_object_motion_host (no GPU): the motion table (MOTION_DTYPE [n]) of objects as a history
+    was captured with (old_objs) and as they are now (new_objs), index by index."""
+    L = _lib.load()
+    a = np.ascontiguousarray(old_objs, dtype=OBJECT_DTYPE).reshape(-1)
+    b = np.ascontiguousarray(new_objs, dtype=OBJECT_DTYPE).reshape(-1)
+    if a.shape != b.shape:
+        raise ValueError(f"object_motion_host: {a.size} old objects for {b.size} new ones")
+    out = np.zeros(a.size, dtype=MOTION_DTYPE)
+    check(L.cpt_object_motion_host(_p(a) if a.size else None, _p(b) if a.size else None, int(a.size), _p(out) if a.size else None))
+    return out
+
+
+def _motion_arg(motion):
+    if motion is None:
+        return None, 0
+    m = np.ascontiguousarray(motion, dtype=MOTION_DTYPE).reshape(-1)
+    return m, int(m.size)
+
+
+def reproject_tracked_host(cam0, cam1, dir0, dir1, id0, t0, id1, t1, normal1, accum, motion, max_history=32, plane_tol=1e-2):
+    """cpt_reproject_tracked_host (no GPU): reproject_host with the motion table (object_motion_host's;
+    None: nothing moved) between the captured frame (cam0, id0, t0) and the new one."""
+    L = _lib.load()
+    a = np.ascontiguousarray(np.array(cam0, dtype=CAMERA_DTYPE))
+    b = np.ascontiguousarray(np.array(cam1, dtype=CAMERA_DTYPE))
+    W, H = int(a["width"].reshape(-1)[0]), int(a["height"].reshape(-1)[0])
+    n = W * H
+    f32 = lambda v, shape: np.ascontiguousarray(v, dtype=np.float32).reshape(shape)
+    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32).reshape(n)
+    d0, d1, nn, acc = f32(dir0, (n, 3)), f32(dir1, (n, 3)), f32(normal1, (n, 3)), f32(accum, (n, 4))
+    i0, i1, tt0, tt1 = i32(id0), i32(id1), f32(t0, n), f32(t1, n)
+    m, n_objs = _motion_arg(motion)
+    out = np.zeros((n, 4), dtype=np.float32)
+    check(L.cpt_reproject_tracked_host(_p(a), _p(b), W, H, _p(d0), _p(d1), _p(i0), _p(tt0), _p(i1), _p(tt1), _p(nn), _p(acc),
+                                       _p(m) if n_objs else None, n_objs, int(max_history), ctypes.c_float(plane_tol), _p(out)))
+    return out
+
+
+def reproject_display_tracked_host(cam0, cam1, dir0, dir1, id0, t0, id1, t1, normal1, mean, count, motion, max_history=32,
+                                   plane_tol=1e-2):
+    """cpt_reproject_display_tracked_host (no GPU): reproject_display_host with the motion table."""
+    L = _lib.load()
+    a = np.ascontiguousarray(np.array(cam0, dtype=CAMERA_DTYPE))
+    b = np.ascontiguousarray(np.array(cam1, dtype=CAMERA_DTYPE))
+    W, H = int(a["width"].reshape(-1)[0]), int(a["height"].reshape(-1)[0])
+    n = W * H
+    f32 = lambda v, shape: np.ascontiguousarray(v, dtype=np.float32).reshape(shape)
+    i32 = lambda v: np.ascontiguousarray(v, dtype=np.int32).reshape(n)
+    d0, d1, nn, mm, c = f32(dir0, (n, 3)), f32(dir1, (n, 3)), f32(normal1, (n, 3)), f32(mean, (n, 3)), f32(count, n)
+    i0, i1, tt0, tt1 = i32(id0), i32(id1), f32(t0, n), f32(t1, n)
+    m, n_objs = _motion_arg(motion)
+    mean_out, count_out = np.zeros((n, 3), dtype=np.float32), np.zeros(n, dtype=np.float32)
+    check(L.cpt_reproject_display_tracked_host(_p(a), _p(b), W, H, _p(d0), _p(d1), _p(i0), _p(tt0), _p(i1), _p(tt1), _p(nn), _p(mm),
+                                               _p(c), _p(m) if n_objs else None, n_objs, int(max_history),
+                                               ctypes.c_float(plane_tol), _p(mean_out), _p(count_out)))
     return mean_out, count_out
 
 
@@ -374,9 +433,38 @@ class Renderer:
         self._check(self._L.cpt_reproject_display(self._ctx, _p(a), _p(b), int(max_history), ctypes.c_float(plane_tol),
                                                   int(flags)))
 
+    def history_capture(self, cam, flags=0):
+        """cpt_history_capture: makes the frame as rendered at `cam` (after camera_get_copy) the
+        captured history of the tracked calls: cam's G-buffer in the current scene (read_gbuffer
+        returns it), cam itself and a snapshot of the objects.  Asynchronous."""
+        c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
+        self._check(self._L.cpt_history_capture(self._ctx, _p(c), int(flags)))
+
+    def history_info(self):
+        """cpt_history_info: (whether a history is captured, its camera or None)."""
+        valid = ctypes.c_int(0)
+        cam = np.zeros((), dtype=CAMERA_DTYPE)
+        self._check(self._L.cpt_history_info(self._ctx, ctypes.byref(valid), _p(cam)))
+        return bool(valid.value), (cam if valid.value else None)
+
+    def reproject_accum_tracked(self, cam_to, max_history=32, plane_tol=1e-2, flags=0):
+        """cpt_reproject_accum_tracked: reproject_accum from the captured history to cam_to through
+        the object edits since the capture (each new hit is looked up where its object stood then;
+        objects whose type or material changed restart).  One trace; cam_to, its G-buffer and the
+        current objects become the captured history.  Asynchronous."""
+        b = np.ascontiguousarray(np.array(cam_to, dtype=CAMERA_DTYPE))
+        self._check(self._L.cpt_reproject_accum_tracked(self._ctx, _p(b), int(max_history), ctypes.c_float(plane_tol), int(flags)))
+
+    def reproject_display_tracked(self, cam_to, max_history=32, plane_tol=1e-2, flags=0):
+        """cpt_reproject_display_tracked: reproject_accum_tracked's look-up applied to the display
+        state, as reproject_display is to reproject_accum.  Asynchronous."""
+        b = np.ascontiguousarray(np.array(cam_to, dtype=CAMERA_DTYPE))
+        self._check(self._L.cpt_reproject_display_tracked(self._ctx, _p(b), int(max_history), ctypes.c_float(plane_tol), int(flags)))
+
     def last_reproject_ms(self, split=False):
-        """Device time of the last reproject_accum or reproject_display, all its launches (HIP events); waits for it.
-        split: (trace at cam_from, trace at cam_to, look-up kernel) instead of their total."""
+        """Device time of the last reproject_accum, reproject_display or tracked variant of either, all its
+        launches (HIP events); waits for it.  split: (trace at cam_from, trace at cam_to, look-up kernel)
+        instead of their total; after a tracked call, which does not trace at cam_from, the first is 0."""
         if split:
             ms3 = (ctypes.c_float * 3)()
             self._check(self._L.cpt_last_reproject_launch_ms(self._ctx, ms3))

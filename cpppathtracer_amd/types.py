@@ -9,6 +9,7 @@ here can cross the C-ABI (include/cpt.h) unchanged:
 * ``OBJECT_DTYPE`` — ``Object`` (include/object.h:17-32), 72 B: type @0, material @8,
   center @48, radius @60, y_pos @64, height @68.
 * ``CAMERA_DTYPE`` — ``MotionalCamera`` (include/motional_camera.h:8-24), 136 B.
+* ``MOTION_DTYPE`` — ``cpt_object_motion`` (cpt.h; no reference counterpart), 40 B.
 """
 import numpy as np
 
@@ -56,6 +57,18 @@ CAMERA_DTYPE = np.dtype(
 )
 
 assert MATERIAL_DTYPE.itemsize == 40 and OBJECT_DTYPE.itemsize == 72 and CAMERA_DTYPE.itemsize == 136
+
+# cpt_motion_kind and cpt_object_motion (cpt.h): where an object stood when the
+# history was captured, 40 B: kind @0, c0 @4, c1 @16, s_xz @28, s_y @32.
+MOTION_SAME, MOTION_SPHERE, MOTION_CYLINDER, MOTION_PLATFORM, MOTION_DROP = 0, 1, 2, 3, 4
+MOTION_DTYPE = np.dtype(
+    {
+        "names": ["kind", "c0", "c1", "s_xz", "s_y"],
+        "formats": ["<i4", ("<f4", 3), ("<f4", 3), "<f4", "<f4"],
+        "offsets": [0, 4, 16, 28, 32],
+        "itemsize": 40,
+    }
+)
 
 
 def make_material(mtype=DIFFUSE, kd=(0.0, 0.0, 0.0), refractive_index=0.0, emit_intensity=0.0,

@@ -4,14 +4,18 @@
 //   cpt_headless [--scene s3|s4|s1000] [--width W] [--height H] [--spp N] [--depth D] [--seed S]
 //                [--out radiance.bin] [--dispatch K --bgra frame.bin] [--pfm image.pfm]
 //                [--texture file.ppm|file.cptex] [--dump-scene objects.bin] [--devices N]
-//                [--objects N] [--animate K] [--pick X,Y] [--orbit N [--reproject]]
-//                [--orbit N --display-reproject on|off --bgra frame.bin]
+//                [--objects N] [--animate K [--animate-step X]] [--pick X,Y] [--orbit N [--reproject]]
+//                [--orbit N [--animate K] --display-reproject on|off|edits --bgra frame.bin]
+//                [--animate K --reproject]
 //
 // --orbit N --display-reproject on|off drives the DispatchRay pipeline through the same orbit: --spp
 // passes at each of the N cameras (each waited for), every move followed by MotionalCamera::Refresh
 // as the reference's viewer does, and writes the last BGRA8 frame to --bgra.  `on` sets
 // PathTracer::SetDisplayReprojection, which carries the running mean to each new camera; `off` is
-// the reference's loop, a fresh mean after every move.
+// the reference's loop, a fresh mean after every move.  With --animate K the loop goes on for K
+// more frames of --spp passes at the last camera, every tenth object moved before each (no
+// Refresh); `edits` sets SetDisplayReprojection's through_edits, which carries the mean through
+// those edits as well, where `on` keeps the stale mean and `off` the reference's.
 //
 // --orbit N renders N frames of --spp passes each into one accumulator while the camera turns about
 // the vertical axis through its look-at point, one degree per frame.  Without --reproject the
@@ -33,9 +37,11 @@
 // (Material::have_tex_/tex_, material.h:21-25) sampling that file (AddTexByFile defaults).
 //
 // --animate K renders K more frames after the first (spp each, not accumulated; the RNG streams
-// continue), moving every 10th object (indices 1, 11, 21, ...) by +0.75 in x before each one
+// continue), moving every 10th object (indices 1, 11, 21, ...) by +0.75 (--animate-step) in x before each one
 // through SceneBVH::UpdateObject (a device refit of both trees), and prints each frame's time.
-// --out then holds the last frame.
+// --out then holds the last frame.  With --reproject the K frames are added to the first frame's
+// accumulator instead, PathTracer::CaptureHistory before the first edit and ReprojectTracked after
+// each carrying the history to where the objects moved.
 // --out writes the raw accumulator mean as float32 rgb (row-major); --dispatch runs K passes
 // through the asynchronous DispatchRay pipeline (1 spp + denoise + mix per pass, callback on
 // the render thread) and writes the last BGRA8 frame to --bgra.
@@ -172,6 +178,7 @@ int main(int argc, char** argv) {
     // (PathTracer::FilterRadiance, 5 levels by default); --pfm then gets the filtered image
     int filter_levels = -1;
     int orbit = 0;
+    float animate_step = 0.75f;
     bool reproject = false;
     std::string display_reproject;   // "", "on" or "off"
     for (int i = 1; i < argc; i += 2) {
@@ -204,6 +211,7 @@ int main(int argc, char** argv) {
         else if (k == "--devices") devices = std::stoi(v);
         else if (k == "--objects") n_objects = std::stoi(v);
         else if (k == "--animate") animate = std::stoi(v);
+        else if (k == "--animate-step") animate_step = std::stof(v);
         else if (k == "--pick") pick = v;
         else if (k == "--orbit") orbit = std::stoi(v);
         else if (k == "--display-reproject") display_reproject = v;
@@ -275,12 +283,12 @@ int main(int argc, char** argv) {
     }
 
     if (!display_reproject.empty()) {
-        if (orbit <= 0 || (display_reproject != "on" && display_reproject != "off")) {
-            fprintf(stderr, "--display-reproject wants on or off, and --orbit N\n");
+        if (orbit <= 0 || (display_reproject != "on" && display_reproject != "off" && display_reproject != "edits")) {
+            fprintf(stderr, "--display-reproject wants on, off or edits, and --orbit N\n");
             return 2;
         }
         FrameSink sink;
-        if (!tracer.SetDisplayReprojection(display_reproject == "on")) {
+        if (!tracer.SetDisplayReprojection(display_reproject != "off", 32, 1e-2f, display_reproject == "edits")) {
             fprintf(stderr, "SetDisplayReprojection: %s\n", tracer.LastError().c_str());
             return 1;
         }
@@ -288,14 +296,19 @@ int main(int argc, char** argv) {
         const float c = 0.99984770f, s = 0.01745241f;   // the orbit of --orbit below
         float dx = cam->origin_.x - cam->look_at_.x, dz = cam->origin_.z - cam->look_at_.z;
         int sent = 0;
-        for (int f = 0; f < orbit; ++f) {
-            if (f > 0) {
+        for (int f = 0; f < orbit + animate; ++f) {
+            if (f > 0 && f < orbit) {
                 const float nx = c * dx + s * dz, nz = c * dz - s * dx;
                 dx = nx;
                 dz = nz;
                 cam->SetOrigin(cam->look_at_.x + dx, cam->origin_.y, cam->look_at_.z + dz);
                 cam->Refresh();
             }
+            if (f >= orbit)   // --animate: the camera stays, every tenth object moves (no Refresh)
+                for (size_t i = 1; i < g_objects.size(); i += 10) {
+                    g_objects[i]->center_.x += animate_step;
+                    SceneBVH::UpdateObject(g_objects[i]);
+                }
             for (int p = 0; p < spp; ++p) {
                 tracer.DispatchRay(DispatchRayArgs{&sink, on_frame});
                 ++sent;
@@ -310,7 +323,8 @@ int main(int argc, char** argv) {
             }
         }
         tracer.Stop();
-        printf("orbit: %d cameras of %d display passes, display reprojection %s\n", orbit, spp, display_reproject.c_str());
+        printf("orbit: %d cameras and %d edited frames of %d display passes, display reprojection %s\n", orbit, animate, spp,
+               display_reproject.c_str());
         if (!bgra_out.empty()) {
             std::ofstream f(bgra_out, std::ios::binary);
             f.write(reinterpret_cast<const char*>(sink.last.data()), (std::streamsize)sink.last.size());
@@ -374,15 +388,18 @@ int main(int argc, char** argv) {
         }
         printf("orbit: %d frames of %d spp%s\n", orbit, spp, reproject ? ", reprojected" : "");
     } else if (!tracer.Render(spp, false)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
+    if (animate > 0 && reproject && !tracer.CaptureHistory()) { fprintf(stderr, "CaptureHistory: %s\n", tracer.LastError().c_str()); return 1; }
     for (int f = 1; f <= animate; ++f) {
         const auto t0 = std::chrono::steady_clock::now();
         int moved = 0;
         for (size_t i = 1; i < g_objects.size(); i += 10) {
-            g_objects[i]->center_.x += 0.75f;
+            g_objects[i]->center_.x += animate_step;
             SceneBVH::UpdateObject(g_objects[i]);
             ++moved;
         }
-        if (!tracer.Render(spp, false)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
+        // --reproject: the frames join one accumulator, its history following the moved objects
+        if (reproject && !tracer.ReprojectTracked()) { fprintf(stderr, "ReprojectTracked: %s\n", tracer.LastError().c_str()); return 1; }
+        if (!tracer.Render(spp, reproject)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         printf("frame %d: %d objects moved, update + render %.3f ms\n", f, moved, ms);
     }

@@ -12,7 +12,7 @@
 //   SetMaxRecursionDepth, SetSeed, SetDevice, SetDevices (row tiling over several GPUs),
 //   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance,
 //   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
-//   Reproject, SetDisplayReprojection, GetStats, Stop.
+//   Reproject, CaptureHistory, ReprojectTracked, SetDisplayReprojection, GetStats, Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -127,7 +127,26 @@ public:
     // LastError).  A frame narrower or lower than 16 pixels has no display launch region: its loop
     // delivers zero frames, on or off.  With SetDevices(n > 1) the frame context holds no scene to
     // trace, so every Refresh restarts.
-    bool SetDisplayReprojection(bool on, int max_history = 32, float plane_tol = 1e-2f);
+    // through_edits (off by default: the loop above, byte for byte): a pass that follows a Refresh
+    // or a changed SceneBVH revision of the same build moves the display state with
+    // cpt_reproject_display_tracked, which follows edited objects (UpdateObject) back to where the
+    // history saw them; the first such pass captures the history at the previous pass's camera,
+    // before the edits reach the context, and the loop uses no history but one it captured or
+    // renewed itself (Reproject, CaptureHistory, ReprojectTracked between passes make the next move
+    // capture again; edits that another call already brought to the context restart the display).
+    // A new BuildBVH still restarts.
+    bool SetDisplayReprojection(bool on, int max_history = 32, float plane_tol = 1e-2f, bool through_edits = false);
+    // Reproject through object edits (cpt_history_capture, cpt_reproject_accum_tracked; DESIGN.md
+    // §23).  CaptureHistory(): after a Render, before moving the camera or editing objects: keeps
+    // the current camera's G-buffer and the objects as they are.  ReprojectTracked(): after
+    // UpdateObject calls and / or a camera move: the accumulator is looked up at the current camera
+    // with every hit followed back to where its object stood at the capture (an object whose type
+    // or material changed restarts); the current camera and objects become the captured history,
+    // so the cycle edit, ReprojectTracked, Render(spp, true) repeats without another capture.
+    // Shadows and reflections of moved objects lag as mirrors do in Reproject.  Both return false
+    // with SetDevices(n > 1), as Reproject does.
+    bool CaptureHistory();
+    bool ReprojectTracked(int max_history = 32, float plane_tol = 1e-2f);
     bool GetStats(cpt_stats* out);
     void Stop();                                 // stop the render thread (also in ~PathTracer)
     const std::string& LastError() const { return err_; }
@@ -177,6 +196,11 @@ private:
     std::shared_ptr<MotionalCamera> camera_;
     // SetDisplayReprojection, and the previous pass of the loop: its camera copy and scene state
     bool display_reproject_ = false;
+    bool display_through_edits_ = false;
+    // through_edits: the context's captured history was captured or renewed by the loop, for the
+    // scene revision loop_history_rev_
+    bool loop_history_ = false;
+    uint64_t loop_history_rev_ = 0;
     int display_max_history_ = 32;
     float display_plane_tol_ = 1e-2f;
     bool prev_pass_ = false;

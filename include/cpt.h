@@ -447,7 +447,8 @@ int cpt_last_query_ms(cpt_ctx* ctx, float* ms);
  * plane_tol that is negative or not finite, a flag bit outside CPT_TRAVERSAL_*.  Nothing is written
  * on an error.
  * Limits.  Static scene: both traces walk the current scene, so after cpt_update_objects the caller
- * clears the accumulator or accepts stale history on the moved objects.  Outgoing radiance is
+ * clears the accumulator, accepts stale history on the moved objects, or uses the tracked calls
+ * below (cpt_history_capture, cpt_reproject_accum_tracked).  Outgoing radiance is
  * reused as if it did not depend on the view: mirrors and glass lag until new passes outweigh
  * max_history.  The wrappers' defaults are max_history 32 and plane_tol 1e-2. */
 int cpt_reproject_accum(cpt_ctx* ctx, const cpt_camera* from, const cpt_camera* to, int max_history, float plane_tol,
@@ -497,6 +498,85 @@ int cpt_reproject_display_host(const cpt_camera* cam0, const cpt_camera* cam1, i
                                const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
                                const float* normal1, const float* mean_in, const float* count_in, int max_history,
                                float plane_tol, float* mean_out, float* count_out);
+/* Tracked reprojection: the history kept through object edits as well as camera moves (an addition,
+ * DESIGN.md §23; CPT_ABI_VERSION stays 1).  cpt_reproject_accum and cpt_reproject_display trace the
+ * G-buffer at `from` in the current scene, which is wrong once an object has moved.  Here the
+ * history's G-buffer is kept instead, with its camera and the objects as they were:
+ *   cpt_history_capture(cam)        once, after rendering at cam: traces cam's G-buffer in the
+ *                                   current scene (cpt_read_gbuffer afterwards returns it), copies
+ *                                   its id and distance planes to the history's, remembers cam and
+ *                                   snapshots the objects.  Writes nothing else.
+ *   cpt_update_objects(...)         any number of edits, or none
+ *   cpt_reproject_accum_tracked(to) / cpt_reproject_display_tracked(to)
+ *                                   one trace, at `to` in the current scene, into the frame's
+ *                                   G-buffer; then the look-up of the untracked call with one
+ *                                   change: a new hit point P on object k is first mapped to the
+ *                                   point P0 that object k held at the capture (cpt_object_motion),
+ *                                   P0 is projected into the captured camera, and a tap's own old
+ *                                   hit point is tested against the plane through P0 with the new
+ *                                   normal (all the mappings keep normals).  Objects of kind
+ *                                   CPT_MOTION_DROP end as zeros.  Sky pixels as in the untracked
+ *                                   call.  Then `to`, its id and distance planes (the look-up
+ *                                   kernel writes them to the history's second planes, which are
+ *                                   swapped in: a ping-pong, no extra launch) and the current
+ *                                   objects become the captured history: the next move again
+ *                                   costs one trace.
+ * With no edit since the capture the results are bit for bit those of cpt_reproject_accum(captured
+ * cam, to) / cpt_reproject_display(captured cam, to), and no motion table is uploaded.
+ * Side effects, asynchrony, argument checks and errors are the untracked calls' (nothing is written
+ * on an error; the display variant keeps its "no display pass yet" and band errors), and
+ * CPT_ERR_STATE when no history is captured.  cpt_set_scene and cpt_set_frame drop the captured
+ * history, and so do cpt_reproject_accum and cpt_reproject_display, which trace their `from` into the
+ * history's planes: a tracked call after an untracked one needs a new cpt_history_capture.  The
+ * captured history describes one frame: the caller applies it to the accumulator or display state
+ * that was rendered at the captured camera with the captured objects (cpt_history_info returns the
+ * camera), and captures again after rendering elsewhere without a tracked call; cpt_update_object(s) and cpt_update_objects_rebuild keep it (ids are AddObject indices
+ * through both).  cpt_last_reproject_ms / _launch_ms time tracked calls too; ms3[0], the trace that
+ * did not run, reads 0.  A call after an edit derives the motion table on the host and uploads it
+ * on the stream from one of two host copies used by turns; it waits on the host only for the upload
+ * of the edited call before the last, if that is still queued.
+ * Limits.  Only first-hit geometry is followed: a moved object's shadow and its reflection in
+ * other objects lag until new passes outweigh max_history, as view-dependent radiance does in the
+ * untracked calls.  No rotation (the primitives have none), no texture-coordinate changes, one
+ * device, full frames. */
+enum cpt_motion_kind {
+    CPT_MOTION_SAME = 0,      /* geometry and material bytewise equal: P0 = P, untouched */
+    CPT_MOTION_SPHERE = 1,    /* P0 = c0 + (P - c1) * (r0 / r1) */
+    CPT_MOTION_CYLINDER = 2,  /* x, z as the sphere; y: c0.y + (P.y - c1.y) * (h0 / h1) */
+    CPT_MOTION_PLATFORM = 3,  /* P0 = (P.x, y_pos0, P.z) */
+    CPT_MOTION_DROP = 4       /* no history: the type or any material field changed, a radius or
+                               * height used as a divisor is not finite or <= 0, or a scale is not
+                               * finite */
+};
+/* One object's motion since the capture, 40 bytes: c0 / c1 the centre then and now (a platform:
+ * y = its y_pos), s_xz = r0 / r1 and s_y = h0 / h1 (a sphere: r0 / r1), each formed once. */
+typedef struct cpt_object_motion {
+    int32_t kind;              /* @0  cpt_motion_kind */
+    cpt_float3 c0;             /* @4  */
+    cpt_float3 c1;             /* @16 */
+    float s_xz;                /* @28 */
+    float s_y;                 /* @32 */
+    int32_t pad_;              /* @36 */
+} cpt_object_motion;
+int cpt_history_capture(cpt_ctx* ctx, const cpt_camera* cam, uint32_t flags);
+int cpt_reproject_accum_tracked(cpt_ctx* ctx, const cpt_camera* to, int max_history, float plane_tol, uint32_t flags);
+int cpt_reproject_display_tracked(cpt_ctx* ctx, const cpt_camera* to, int max_history, float plane_tol, uint32_t flags);
+/* Whether a history is captured (*valid 0 / 1) and, when cam is not NULL and one is, its camera. */
+int cpt_history_info(cpt_ctx* ctx, int* valid, cpt_camera* cam);
+/* HOST ONLY, no GPU: the motion table of n objects as captured (old_objs) and as they are now
+ * (new_objs), out_table [n]; and the functions the tracked kernels run, shaped like
+ * cpt_reproject_host / cpt_reproject_display_host with the table of n_objs records (NULL with 0:
+ * nothing moved).  An id1 outside [0, n_objs) with a table: CPT_ERR_INVALID_ARG. */
+int cpt_object_motion_host(const cpt_object* old_objs, const cpt_object* new_objs, int n, cpt_object_motion* out_table);
+int cpt_reproject_tracked_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0,
+                               const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
+                               const float* normal1, const float* accum_in, const cpt_object_motion* table, int n_objs,
+                               int max_history, float plane_tol, float* accum_out);
+int cpt_reproject_display_tracked_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height,
+                                       const float* dir0, const float* dir1, const int32_t* id0, const float* t0,
+                                       const int32_t* id1, const float* t1, const float* normal1, const float* mean_in,
+                                       const float* count_in, const cpt_object_motion* table, int n_objs, int max_history,
+                                       float plane_tol, float* mean_out, float* count_out);
 /* Device-to-device copy of the accumulator (e.g. into an RCCL send buffer), ordered against the
  * caller's HIP stream `caller_stream` (NULL: the null stream) without blocking the host: the
  * context's stream first waits for the work queued on caller_stream so far (a fill of dst, a
