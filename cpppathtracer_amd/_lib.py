@@ -40,6 +40,9 @@ PROTOTYPES = {
     "cpt_read_rng": (_I, [_P, _P]),
     "cpt_write_rng": (_I, [_P, _P]),
     "cpt_render": (_I, [_P, _P, _I, _I, _U32]),
+    "cpt_render_to_count": (_I, [_P, _P, _I, _I, _U32]),
+    "cpt_topup_info": (_I, [_P, _P, _P, _P]),
+    "cpt_topup_deficit_host": (_I, [ctypes.c_float, _I, _P]),
     "cpt_synchronize": (_I, [_P]),
     "cpt_read_accum": (_I, [_P, _P]),
     "cpt_clear_accum": (_I, [_P]),
@@ -127,8 +130,10 @@ CPT_SCHEDULE_COST = 0x800
 CPT_SCHEDULE_CONSOLIDATE = 0x1000
 CPT_SCHEDULE_NO_CONSOLIDATE = 0x2000
 CPT_SCHEDULE_PREVIOUS = 0x4000
+CPT_TILE_ORDER_TOPUP = 4
 CPT_ERR_INVALID_ARG = 1
 CPT_ERR_STATE = 5
+CPT_ERR_UNSUPPORTED = 6
 CPT_ERR_DEVICE = 7   # a kernel abandoned work (reported at the next synchronising call)
 
 

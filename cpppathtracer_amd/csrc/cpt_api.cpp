@@ -716,6 +716,35 @@ bool PathTracer::Render(int spp, bool accumulate) {
     return RenderPass(cma, spp, accumulate);
 }
 
+// Top-up render (cpt_render_to_count): as RenderPass, every row tile on its own
+// accumulator, then the gather.
+bool PathTracer::RenderToCount(int target) {
+    if (!camera_) {
+        err_ = "RenderToCount: SetCamera first";
+        return false;
+    }
+    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
+    MotionalCamera cam = camera_->GetCopy();
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!SyncScene() || !EnsureFrame(cam)) return false;
+    const uint32_t flags = CPT_RENDER_AUX | (ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u);
+    const cpt_camera* c = reinterpret_cast<const cpt_camera*>(&cam);
+    if (!frame_) {
+        if (cpt_render_to_count(tiles_[0].ctx, c, target, (int)max_recursion_depth_, flags | CPT_RENDER_SYNC) != CPT_OK)
+            return Fail("cpt_render_to_count", tiles_[0].ctx);
+        return true;
+    }
+    for (Tile& t : tiles_)
+        if (cpt_render_to_count(t.ctx, c, target, (int)max_recursion_depth_, flags) != CPT_OK)
+            return Fail("cpt_render_to_count", t.ctx);
+    for (Tile& t : tiles_)
+        if (cpt_gather_rows(frame_, t.ctx) != CPT_OK) return Fail("cpt_gather_rows", frame_);
+    if (cpt_synchronize(frame_) != CPT_OK) return Fail("cpt_synchronize", frame_);
+    for (Tile& t : tiles_)   // the tiles' device errors (their work is done by now)
+        if (cpt_synchronize(t.ctx) != CPT_OK) return Fail("cpt_synchronize", t.ctx);
+    return true;
+}
+
 // The adaptive render over row tiles: every tile's first round is queued, then this thread goes
 // round the unfinished tiles, each step reading one tile's round and queueing its next, so every
 // device has a round queued while the host waits on another.  The tiles are whole 8-row blocks, so

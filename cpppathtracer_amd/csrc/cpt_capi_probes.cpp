@@ -54,7 +54,8 @@ int cpt_debug_read_nodes(cpt_ctx* c, void* out, size_t capacity_bytes, size_t* n
 
 int cpt_debug_read_tile_order(cpt_ctx* c, int which, uint32_t* out, size_t capacity, size_t* n) {
     if (!c || !out || !n) return CPT_ERR_INVALID_ARG;
-    if (which < 0 || which > 2) return fail(c, CPT_ERR_INVALID_ARG, "cpt_debug_read_tile_order: which %d (0..2)", which);
+    if (which != CPT_TILE_ORDER_TOPUP && (which < 0 || which > 2))
+        return fail(c, CPT_ERR_INVALID_ARG, "cpt_debug_read_tile_order: which %d (0..2, %d)", which, CPT_TILE_ORDER_TOPUP);
     const Frame& f = c->frame;
     const uint32_t* src = nullptr;   // stays null for the pending round's list without an order: 0, 1, 2, ...
     size_t len = n_tiles(c);
@@ -65,6 +66,15 @@ int cpt_debug_read_tile_order(cpt_ctx* c, int which, uint32_t* out, size_t capac
         src = f.schedule.previous_order();
         if (!f.set || !src)
             return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no CPT_SCHEDULE_PREVIOUS order on this frame");
+    } else if (which == CPT_TILE_ORDER_TOPUP) {
+        if (!f.set || !f.topup.planned) return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no cpt_render_to_count on this frame");
+        // the active prefix: its length is the plan's device word, read behind the queued call
+        src = f.topup.d_order;
+        uint32_t active = 0;
+        if (int rc = sync_checked(c)) return rc;
+        HIP_TRY(c, hipMemcpy(&active, f.topup.d_words, sizeof(active), hipMemcpyDeviceToHost));
+        if (active > len) return fail(c, CPT_ERR_DEVICE, "cpt_debug_read_tile_order: %u of %zu tiles active", active, len);
+        len = active;
     } else {
         if (!f.adaptive.pending.on) return fail(c, CPT_ERR_STATE, "cpt_debug_read_tile_order: no adaptive render is pending");
         src = f.adaptive.pending.p.tile_order;

@@ -3,7 +3,7 @@
 // cpt_capi_render.cpp (render launches, tile schedules, timing), cpt_capi_adaptive.cpp (adaptive
 // render), cpt_capi_filter.cpp (a-trous filter), cpt_capi_gather.cpp (row-tile gather),
 // cpt_capi_display.cpp (display path), cpt_capi_query.cpp (G-buffer, ray queries, picking),
-// cpt_capi_reproject.cpp (reprojection to a moved camera),
+// cpt_capi_reproject.cpp (reprojection to a moved camera), cpt_capi_topup.cpp (top-up render),
 // cpt_capi_probes.cpp (diagnostic probes, self-tests) and
 // cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  Host code only.
 #pragma once
@@ -174,6 +174,13 @@ struct ReprojectState {
     int motion_turn = 0;
 };
 
+// The top-up render (cpt_capi_topup.cpp; allocated on the frame's first cpt_render_to_count).
+struct TopupState {
+    DevBuf<uint32_t> d_order;   // the plan's order: every tile, largest deficit first
+    DevBuf<uint32_t> d_words;   // the plan's record (cpt_topup.hpp PLAN_*): active tiles, pixels, passes
+    bool planned = false;       // a cpt_render_to_count has been queued since cpt_set_frame
+};
+
 struct Frame {
     bool set = false, rng_set = false;
     DevBuf<int32_t> d_rows;
@@ -189,6 +196,7 @@ struct Frame {
     FilterState filter;
     GBufferState gbuffer;
     ReprojectState reproject;
+    TopupState topup;
 };
 
 // A pair of timing events around a subsystem's last launches, once they have been recorded.

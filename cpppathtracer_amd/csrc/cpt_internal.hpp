@@ -64,7 +64,16 @@ struct KParams {
     unsigned long long* stats;  // [5]           (STATS)
     uint32_t* work;         // pixel dequeue counter (zeroed before each launch)
     const uint32_t* tile_order;  // megakernel dequeue order of the 8x8 tiles (nullptr: row-major)
-    uint32_t* tile_cost;    // pilot launch only: per-tile work (cost schedule)
+    // One pointer slot, two launches that never coincide (a TOPUP kernel is never a PROBE kernel):
+    union {
+        uint32_t* tile_cost;           // pilot launch only: per-tile work (cost schedule)
+        // Top-up launch only (cpt_render_to_count, the TOPUP kernels): the device word that holds
+        // how many entries of tile_order have a deficit (cpt_topup.hip's plan); they alone are
+        // dequeued.  spp is then the target, a lane's passes its pixel's deficit (cpt_topup.hpp).
+        // In the pilot's slot, not appended: a longer KParams moves the hidden arguments of every
+        // kernel that takes one, and the explicit ones behind it, by 8 bytes.
+        const uint32_t* topup_active;
+    };
     int spp, max_depth, accumulate;
     int lanes;              // lanes per wave that take pixels (64; fewer: DIAGNOSTIC CPT_LANES_PER_WAVE)
     int replicate;          // lanes per taken pixel (1; more: DIAGNOSTIC CPT_REPLICATE, identical copies)
@@ -231,6 +240,9 @@ hipError_t launch_refit(const RefitLeaf* leaves_in, int n_leaves, const int32_t*
                         Node* leaves, hipStream_t stream);
 
 hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, LaunchGrid& grid, hipStream_t stream);
+// The top-up launch (p.topup_active and p.tile_order from the plan, p.spp the target): the TOPUP
+// kernels, never consolidating, on a grid sized for the whole frame.
+hipError_t launch_megakernel_topup(const KParams& p, bool stats, bool aux, LaunchGrid& grid, hipStream_t stream);
 // The resident workgroups of the consolidating kernel such a launch runs (consolidation_slab).
 hipError_t consolidating_workgroups(const KParams& p, bool stats, bool aux, LaunchGrid& grid, long long* out);
 hipError_t launch_wavefront(const KParams& p, WfState& w, bool stats, bool aux, LaunchGrid& grid, hipStream_t stream,

@@ -4,9 +4,10 @@
 //                        per-lane path regeneration, state in registers; with what it alone
 //                        uses: Lane, decode_pixel, the coherent load/store helpers
 //                        and the hand-over queue of the tail consolidation
-//   launch_mk*           the STATS / AUX / PROBE / LDS / CONS / HYB ladder; each launch is sized
+//   launch_mk*           the STATS / AUX / PROBE / LDS / CONS / HYB / TOPUP ladder; each launch is sized
 //                        by the context's LaunchGrid (cpt_internal.hpp)
-//   launch_megakernel    the render's entry;  launch_cost_pilot: the cost schedule's pilot
+//   launch_megakernel    the render's entry;  launch_cost_pilot: the cost schedule's pilot;
+//                        launch_megakernel_topup: the top-up render's (the TOPUP kernels)
 //   timeline_read        the CPT_TIMELINE read-out (timeline::g_tl is per translation unit)
 //   k_prepare_materials  per-material constants: GetKd(0,0), emission, 1/alpha — material.cu:43-45,
 //                        69-70, 103-104; here because its register assignment depends on the unit
@@ -21,6 +22,7 @@
 #include <algorithm>
 
 #include "cpt_path.hpp"
+#include "cpt_topup.hpp"
 
 namespace cpt {
 
@@ -174,8 +176,12 @@ template <bool LDST> constexpr int mk_waves() { return LDST ? LDS_BLOCK / 256 : 
 
 // HYB (LDST): the wide tree has more nodes than the LDS image holds; the rest are read from
 // global memory (cpt_path.hpp load_wide_node).
-template <bool STATS, bool AUX, bool PROBE, bool LDST, bool CONS, bool HYB>
+// TOPUP (cpt_render_to_count): a lane's passes are its pixel's deficit to the target
+// p.spp (cpt_topup.hpp), read from the accumulator at the take; a pixel without one is neither
+// loaded nor written.  Only the first *p.topup_active tiles of p.tile_order are dequeued.
+template <bool STATS, bool AUX, bool PROBE, bool LDST, bool CONS, bool HYB, bool TOPUP = false>
 __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakernel(const KParams p) {
+    static_assert(!TOPUP || (!PROBE && !CONS), "a top-up launch writes its pixels and never consolidates");
     constexpr bool COUNT = STATS || PROBE;
     constexpr int BLK = mk_block<LDST>();
     __shared__ uint4 s_tree[LDST ? LDS_TREE_NODES * 7 : 1];
@@ -184,7 +190,9 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
     const int lane = threadIdx.x & 63;
     const size_t npix = (size_t)p.n_rows * p.width;
     // (an adaptive render's later rounds dequeue only the first n_active tiles of p.tile_order)
-    const uint32_t n_work = (p.n_active ? p.n_active : (uint32_t)TileGrid{p.width, p.n_rows}.count()) * 64u;
+    // (a top-up launch: the tiles with a deficit, counted on the device by the plan before it)
+    const uint32_t n_work =
+        (TOPUP ? *p.topup_active : (p.n_active ? p.n_active : (uint32_t)TileGrid{p.width, p.n_rows}.count())) * 64u;
     const uint32_t max_depth = (uint32_t)p.max_depth;
     Counters cnt{};
     uint32_t work_at_take = 0;   // PROBE: the lane's counters when it took its pixel
@@ -352,21 +360,37 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
                         execdiag::lanes(p.stats + 64, 0);
                         L.xy = (uint32_t)x | ((uint32_t)p.rows[ri] << 16);
                         L.pix = (uint32_t)ri * (uint32_t)p.width + (uint32_t)x;
-                        L.load<!PROBE>(p, npix);
-                        L.left = p.spp;
-                        first_normal = mk1(0.f);
-                        if (PROBE) work_at_take = cnt.segments + cnt.nodes + cnt.prims;
-                        if (max_depth == 0) {
-                            // while (0 < 0) never runs: each pass is RayGen's draws and zero radiance
-                            for (; L.left > 0; --L.left) {
-                                (void)ray_gen(p, (int)(L.xy & 0xffffu), (int)(L.xy >> 16), L.s);
-                                L.sum = L.sum + mk1(0.f);
-                                L.passes += 1.0f;
+                        bool owed = true;   // TOPUP: the pixel has a deficit
+                        if constexpr (TOPUP) {
+                            // the accumulator first: a pixel at its target is done here, its RNG
+                            // planes not read and nothing of it written
+                            const float4 a = p.accum[L.pix];
+                            L.left = topup::deficit(a.w, p.spp);
+                            owed = L.left > 0;
+                            if (owed) {
+                                load_rng(p, npix, L.pix, L.s);
+                                L.sum = mk(a.x, a.y, a.z);
+                                L.passes = a.w;
                             }
+                        } else {
+                            L.load<!PROBE>(p, npix);
+                            L.left = p.spp;
                         }
-                        busy = true;
-                        took = true;
-                        begin = L.left > 0;
+                        if (owed) {
+                            first_normal = mk1(0.f);
+                            if (PROBE) work_at_take = cnt.segments + cnt.nodes + cnt.prims;
+                            if (max_depth == 0) {
+                                // while (0 < 0) never runs: each pass is RayGen's draws and zero radiance
+                                for (; L.left > 0; --L.left) {
+                                    (void)ray_gen(p, (int)(L.xy & 0xffffu), (int)(L.xy >> 16), L.s);
+                                    L.sum = L.sum + mk1(0.f);
+                                    L.passes += 1.0f;
+                                }
+                            }
+                            busy = true;
+                            took = true;
+                            begin = L.left > 0;
+                        }
                     }
                 }
                 if (cons) {   // live chains (taken, not finished): the consolidation's measure
@@ -619,17 +643,17 @@ __global__ void __launch_bounds__(mk_block<LDST>(), mk_waves<LDST>()) k_megakern
 // ======================================================================================
 // Host-side launchers (called from cpt_capi_render.cpp and cpt_capi_adaptive.cpp).
 // ======================================================================================
-template <bool S, bool A, bool P, bool T, bool C = false, bool H = false>
+template <bool S, bool A, bool P, bool T, bool C = false, bool H = false, bool U = false>
 static hipError_t launch_mk(const KParams& p, LaunchGrid& g, hipStream_t stream) {
     constexpr int block = mk_block<T>();
     // persistent grid: every resident slot once; lanes pull pixels from p.work.  (The test hook's
     // cap makes lanes take several pixels in turn on small frames; the kernel's gridDim.x follows.)
     const long long tiles = p.n_active ? (long long)p.n_active : (long long)TileGrid{p.width, p.n_rows}.count();
     int grid = 0;
-    const hipError_t e = g.size((const void*)k_megakernel<S, A, P, T, C, H>, block,
+    const hipError_t e = g.size((const void*)k_megakernel<S, A, P, T, C, H, U>, block,
                                 megakernel_want(tiles, p.lanes, p.replicate, block), true, &grid);
     if (e != hipSuccess || grid < 1) return e;
-    hipLaunchKernelGGL((k_megakernel<S, A, P, T, C, H>), dim3((unsigned)grid), dim3(block), 0, stream, p);
+    hipLaunchKernelGGL((k_megakernel<S, A, P, T, C, H, U>), dim3((unsigned)grid), dim3(block), 0, stream, p);
     return hipGetLastError();
 }
 
@@ -656,6 +680,27 @@ hipError_t launch_megakernel(const KParams& p, bool stats, bool aux, LaunchGrid&
     if (stats) return launch_mk_any<true, false, false>(p, g, stream);
     if (aux) return launch_mk_any<false, true, false>(p, g, stream);
     return launch_mk_any<false, false, false>(p, g, stream);
+}
+
+// The top-up launch (cpt_render_to_count): the TOPUP kernels over STATS x AUX x {no LDS tree, LDST,
+// LDST + HYB}, never consolidating.  p.n_active is 0, so the grid is sized for the whole frame;
+// the workgroups that find the plan's active tiles taken leave at their first take.
+template <bool S, bool A>
+static hipError_t launch_mk_topup(const KParams& p, LaunchGrid& g, hipStream_t stream) {
+    if (!use_lds_tree(p)) return launch_mk<S, A, false, false, false, false, true>(p, g, stream);
+    if (p.n_wide > LDS_TREE_NODES) return launch_mk<S, A, false, true, false, true, true>(p, g, stream);
+    return launch_mk<S, A, false, true, false, false, true>(p, g, stream);
+}
+
+hipError_t launch_megakernel_topup(const KParams& p, bool stats, bool aux, LaunchGrid& g, hipStream_t stream) {
+    if (p.width <= 0 || p.n_rows <= 0) return hipSuccess;
+    if (!p.topup_active || !p.tile_order || p.n_active || p.resume) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(p.work, 0, sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    if (stats && aux) return launch_mk_topup<true, true>(p, g, stream);
+    if (stats) return launch_mk_topup<true, false>(p, g, stream);
+    if (aux) return launch_mk_topup<false, true>(p, g, stream);
+    return launch_mk_topup<false, false>(p, g, stream);
 }
 
 // The resident workgroups of the consolidating kernel launch_mk_lds picks for these flags and

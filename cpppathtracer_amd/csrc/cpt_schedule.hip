@@ -4,6 +4,7 @@
 //   tile_schedule_scratch_bytes      what launch_tile_* need as scratch
 //   launch_tile_schedule             pilot (cpt_megakernel.hip launch_cost_pilot) + sort
 //   launch_tile_order_from_draws     CPT_SCHEDULE_PREVIOUS: draws + sort
+//   sort_tiles_by_key                the top-up plan's order (cpt_topup.hip): the sort alone
 //
 // The only unit that includes hipcub (its radix sort's rocprim kernels).  The reference has no
 // counterpart: it launches one thread per pixel in raster order (path_tracer.cu:124-133).
@@ -13,6 +14,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "cpt_path.hpp"
+#include "cpt_topup.hpp"
 
 namespace cpt {
 
@@ -118,5 +120,12 @@ hipError_t launch_tile_schedule(const KParams& p0, int passes, void* scratch, si
     e = launch_cost_pilot(p, grid, stream);
     if (e != hipSuccess) return e;
     return sort_tiles_by_cost(s, n, order, stream);
+}
+
+// The top-up plan's order (cpt_topup.hip): the same sort on keys the caller left in the scratch's
+// first n words.  The radix sort is stable and the ids ascend, so equal keys stay row-major.
+hipError_t sort_tiles_by_key(void* scratch, size_t scratch_bytes, int n, uint32_t* order, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    return sort_tiles_by_cost(carve_tile_scratch(scratch, scratch_bytes, n), n, order, stream);
 }
 }  // namespace cpt

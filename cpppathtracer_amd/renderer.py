@@ -38,6 +38,15 @@ def camera_get_copy(cam):
     return c
 
 
+def topup_deficit_host(count, target):
+    """cpt_topup_deficit_host (no GPU): the passes a pixel whose accumulator count is `count` (a
+    float32) lacks to `target`, the rule render_to_count's kernels run."""
+    L = _lib.load()
+    d = ctypes.c_int(-1)
+    check(L.cpt_topup_deficit_host(ctypes.c_float(np.float32(count)), int(target), ctypes.byref(d)))
+    return d.value
+
+
 def reproject_host(cam0, cam1, dir0, dir1, id0, t0, id1, t1, normal1, accum, max_history=32, plane_tol=1e-2):
     """cpt_reproject_host (no GPU): the function reproject_accum's kernel runs, on host arrays.  cam0 /
     cam1 after camera_get_copy; dir0 / dir1 [npix, 3] their centre-ray directions; (id0, t0) and
@@ -272,6 +281,27 @@ class Renderer:
         if consolidate is not None:
             f |= CPT_SCHEDULE_CONSOLIDATE if consolidate else CPT_SCHEDULE_NO_CONSOLIDATE
         self._check(self._L.cpt_render(self._ctx, _p(c), spp, max_depth, f))
+
+    def render_to_count(self, cam, target, max_depth, aux=False, stats=False, sync=False, flags=0):
+        """cpt_render_to_count: every pixel runs the passes its accumulator count lacks to `target`
+        (topup_deficit_host's rule), continuing its RNG stream and adding to its accumulator as an
+        accumulating render of that many passes would; a pixel at or past the target is not
+        written at all.  One plan (tiles keyed by their largest deficit, sorted) and one megakernel
+        launch over the tiles with a deficit.  `flags`: CPT_TRAVERSAL_* bits (not the wavefront
+        path, no CPT_SCHEDULE_PREVIOUS / _COST / _CONSOLIDATE).  Asynchronous unless sync."""
+        c = np.ascontiguousarray(np.array(cam, dtype=CAMERA_DTYPE))
+        f = int(flags)
+        f |= CPT_RENDER_AUX if aux else 0
+        f |= CPT_RENDER_STATS if stats else 0
+        f |= CPT_RENDER_SYNC if sync else 0
+        self._check(self._L.cpt_render_to_count(self._ctx, _p(c), int(target), int(max_depth), f))
+
+    def topup_info(self):
+        """cpt_topup_info of the last render_to_count: {"tiles", "pixels", "passes"}, the 8x8 tiles
+        and the pixels with a deficit and the sum of the deficits.  Waits for the call."""
+        tiles, pixels, passes = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self._L.cpt_topup_info(self._ctx, ctypes.byref(tiles), ctypes.byref(pixels), ctypes.byref(passes)))
+        return {"tiles": int(tiles.value), "pixels": int(pixels.value), "passes": int(passes.value)}
 
     def render_adaptive(self, cam, min_spp, max_spp, batch, rel_error, max_depth, flags=0):
         """cpt_render_adaptive: rounds of `batch` passes over the 8x8 tiles whose pixels have not all
@@ -613,7 +643,8 @@ class Renderer:
     def debug_tile_order(self, which):
         """DIAGNOSTIC: a device-built tile list (cpt_debug_read_tile_order) as uint32 tile ids:
         which = 0 the cost schedule's order, 1 the CPT_SCHEDULE_PREVIOUS order, 2 the list the
-        pending adaptive round renders.  Waits for the context's stream."""
+        pending adaptive round renders, 4 (CPT_TILE_ORDER_TOPUP) the tiles the last render_to_count
+        rendered, largest deficit first.  Waits for the context's stream."""
         ty, tx = tile_grid(self.width, self.n_rows)
         out = np.zeros(max(1, ty * tx), dtype=np.uint32)
         n = ctypes.c_size_t(0)

@@ -6,7 +6,11 @@
 //                [--texture file.ppm|file.cptex] [--dump-scene objects.bin] [--devices N]
 //                [--objects N] [--animate K [--animate-step X]] [--pick X,Y] [--orbit N [--reproject]]
 //                [--orbit N [--animate K] --display-reproject on|off|edits --bgra frame.bin]
-//                [--animate K --reproject]
+//                [--animate K --reproject] [--fill T]
+//
+// --fill T (with --orbit N --reproject, and with --animate K --reproject): each frame after the
+// first is topped up to T passes per pixel (PathTracer::RenderToCount) instead of
+// given --spp uniform passes: the passes go to the pixels the reprojection left short.
 //
 // --orbit N --display-reproject on|off drives the DispatchRay pipeline through the same orbit: --spp
 // passes at each of the N cameras (each waited for), every move followed by MotionalCamera::Refresh
@@ -178,6 +182,7 @@ int main(int argc, char** argv) {
     // (PathTracer::FilterRadiance, 5 levels by default); --pfm then gets the filtered image
     int filter_levels = -1;
     int orbit = 0;
+    int fill = 0;   // --fill T: frames after the first are topped up to T passes (0: --spp uniform passes)
     float animate_step = 0.75f;
     bool reproject = false;
     std::string display_reproject;   // "", "on" or "off"
@@ -214,6 +219,7 @@ int main(int argc, char** argv) {
         else if (k == "--animate-step") animate_step = std::stof(v);
         else if (k == "--pick") pick = v;
         else if (k == "--orbit") orbit = std::stoi(v);
+        else if (k == "--fill") fill = std::stoi(v);
         else if (k == "--display-reproject") display_reproject = v;
         else if (k == "--adaptive") adaptive = std::stof(v);
         else if (k == "--min-spp") min_spp = std::stoi(v);
@@ -282,6 +288,10 @@ int main(int argc, char** argv) {
         return 0;
     }
 
+    if (fill != 0 && (fill < 1 || !reproject || (orbit <= 0 && animate <= 0))) {
+        fprintf(stderr, "--fill wants T >= 1 and --reproject with --orbit N or --animate K\n");
+        return 2;
+    }
     if (!display_reproject.empty()) {
         if (orbit <= 0 || (display_reproject != "on" && display_reproject != "off" && display_reproject != "edits")) {
             fprintf(stderr, "--display-reproject wants on, off or edits, and --orbit N\n");
@@ -384,9 +394,13 @@ int main(int argc, char** argv) {
                 cam->SetOrigin(cam->look_at_.x + dx, cam->origin_.y, cam->look_at_.z + dz);
                 if (reproject && !tracer.Reproject(from)) { fprintf(stderr, "Reproject: %s\n", tracer.LastError().c_str()); return 1; }
             }
-            if (!tracer.Render(spp, f > 0)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
+            if (f > 0 && fill > 0) {
+                if (!tracer.RenderToCount(fill)) { fprintf(stderr, "RenderToCount: %s\n", tracer.LastError().c_str()); return 1; }
+            } else if (!tracer.Render(spp, f > 0)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
         }
-        printf("orbit: %d frames of %d spp%s\n", orbit, spp, reproject ? ", reprojected" : "");
+        printf("orbit: %d frames of %d spp%s", orbit, spp, reproject ? ", reprojected" : "");
+        if (fill > 0) printf(", topped up to %d", fill);
+        printf("\n");
     } else if (!tracer.Render(spp, false)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
     if (animate > 0 && reproject && !tracer.CaptureHistory()) { fprintf(stderr, "CaptureHistory: %s\n", tracer.LastError().c_str()); return 1; }
     for (int f = 1; f <= animate; ++f) {
@@ -399,7 +413,9 @@ int main(int argc, char** argv) {
         }
         // --reproject: the frames join one accumulator, its history following the moved objects
         if (reproject && !tracer.ReprojectTracked()) { fprintf(stderr, "ReprojectTracked: %s\n", tracer.LastError().c_str()); return 1; }
-        if (!tracer.Render(spp, reproject)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
+        if (fill > 0) {
+            if (!tracer.RenderToCount(fill)) { fprintf(stderr, "RenderToCount: %s\n", tracer.LastError().c_str()); return 1; }
+        } else if (!tracer.Render(spp, reproject)) { fprintf(stderr, "Render: %s\n", tracer.LastError().c_str()); return 1; }
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         printf("frame %d: %d objects moved, update + render %.3f ms\n", f, moved, ms);
     }

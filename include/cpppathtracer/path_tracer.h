@@ -12,7 +12,8 @@
 //   SetMaxRecursionDepth, SetSeed, SetDevice, SetDevices (row tiling over several GPUs),
 //   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance,
 //   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
-//   Reproject, CaptureHistory, ReprojectTracked, SetDisplayReprojection, GetStats, Stop.
+//   Reproject, CaptureHistory, ReprojectTracked, RenderToCount, SetDisplayReprojection, GetStats,
+//   Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -146,6 +147,13 @@ public:
     // Shadows and reflections of moved objects lag as mirrors do in Reproject.  Both return false
     // with SetDevices(n > 1), as Reproject does.
     bool CaptureHistory();
+    // Top-up render (cpt_render_to_count; an addition: the reference gives every
+    // pixel the same passes): every pixel runs the passes its accumulator count lacks to `target`
+    // (1 .. 2^20), as a Render(d, true) of its own deficit d would; pixels at or past the target
+    // are left untouched.  After Reproject / ReprojectTracked it spends the passes on the
+    // disoccluded pixels.  Synchronous.  With SetDevices(n > 1) it runs on every row tile and
+    // gathers, as Render does.
+    bool RenderToCount(int target);
     bool ReprojectTracked(int max_history = 32, float plane_tol = 1e-2f);
     bool GetStats(cpt_stats* out);
     void Stop();                                 // stop the render thread (also in ~PathTracer)

@@ -284,6 +284,38 @@ int cpt_write_aux(cpt_ctx* ctx, const float* normal3, const float* depth);
  * least that).  Synchronous. */
 int cpt_tile_costs(cpt_ctx* ctx, const cpt_camera* cam, int passes, int max_depth, uint32_t flags, uint32_t* out,
                    size_t n_out);
+/* Top-up render (an addition: the reference gives every pixel the same passes,
+ * path_tracer.cu:124-175).  Every pixel of the context runs d further SamplePixel passes, d its
+ * deficit to `target`: with count the pixel's accumulator count (its .w), d = target - (int)count
+ * (truncation) when count is finite and 0 <= count < target, else 0 (at or past the target,
+ * negative, NaN, +-inf).  The passes continue the pixel's XORWOW stream and add to its accumulator
+ * exactly as a cpt_render of d passes with CPT_RENDER_ACCUMULATE would for that pixel.  A pixel with
+ * d == 0 is not written at all: its accumulator, RNG words and (CPT_RENDER_AUX) first-hit normal
+ * and depth keep their bits.  Meant for the frame cpt_reproject_accum[_tracked] leaves, whose
+ * counts are uneven: the passes go to the disoccluded pixels instead of to every pixel alike.
+ *
+ * One plan and one megakernel launch on the context's stream, no host wait: each 8x8 tile is keyed
+ * by its largest deficit, the tiles are sorted by key (descending, ties row-major), and the launch
+ * dequeues the tiles with a deficit in that order, their number read from device memory.
+ * target in [1, 2^20], max_depth in [0, 32], else CPT_ERR_INVALID_ARG.  flags: CPT_TRAVERSAL_*,
+ * CPT_RENDER_STATS, CPT_RENDER_AUX, CPT_RENDER_SYNC; CPT_RENDER_ACCUMULATE is implied and may be
+ * passed.  CPT_ERR_UNSUPPORTED: CPT_PATH_WAVEFRONT, CPT_SCHEDULE_PREVIOUS, CPT_SCHEDULE_COST,
+ * CPT_SCHEDULE_CONSOLIDATE (a top-up launch never consolidates).  State errors as cpt_render's, and
+ * CPT_ERR_STATE while an adaptive render is pending; nothing is written on an error.  Works on
+ * row-tiled contexts as cpt_render does.  Like cpt_render it leaves an adaptive result's moments,
+ * the display state, the G-buffer and the reprojection history as they were.  Asynchronous unless
+ * CPT_RENDER_SYNC; cpt_last_render_ms covers the plan and the launch, cpt_last_kernel_stats the
+ * launch alone. */
+int cpt_render_to_count(cpt_ctx* ctx, const cpt_camera* cam, int target, int max_depth, uint32_t flags);
+/* The last cpt_render_to_count's plan since cpt_set_frame (CPT_ERR_STATE if none; an addition: the
+ * reference gives every pixel the same passes): the 8x8 tiles with a deficit, the pixels with a
+ * deficit and the sum of the deficits (the passes the call runs).  Each output may be NULL.  Waits
+ * for the call. */
+int cpt_topup_info(cpt_ctx* ctx, uint32_t* tiles, uint64_t* pixels, uint64_t* passes);
+/* HOST ONLY, no GPU: the deficit rule above, the function the device runs (an addition: the
+ * reference gives every pixel the same passes).  target outside [1, 2^20] or a NULL d:
+ * CPT_ERR_INVALID_ARG. */
+int cpt_topup_deficit_host(float count, int target, int* d);
 /* Adaptive render (an addition: the reference gives every pixel the same passes,
  * path_tracer.cu:124-175).  Rounds of `batch` passes; after a round every 8x8 tile whose pixels
  * have all converged leaves the list of tiles the next round renders, and so does every tile at
@@ -657,12 +689,15 @@ int cpt_debug_read_nodes(cpt_ctx* ctx, void* out, size_t capacity_bytes, size_t*
  * CPT_SCHEDULE_PREVIOUS rebuild left for the next such render.  which = 2: the list the pending
  * adaptive round renders, between a successful cpt_adaptive_begin and the cpt_adaptive_step that
  * returns 0 (round 1 without the cost schedule has no list on the device: 0, 1, 2, ...).
+ * which = CPT_TILE_ORDER_TOPUP (4): the active prefix of the last cpt_render_to_count's plan, the
+ * tiles with a deficit, largest first, ties row-major (3 stays refused, as any unknown list).
  * CPT_ERR_STATE when the frame holds no such list; CPT_ERR_INVALID_ARG for another `which` or a
  * capacity below the length (nothing written).  WAITS: the copy is queued on the context's stream
  * and the stream is drained, so with which = 2 the call returns after the queued round (which only
  * reads that list: its compaction writes the other buffer).  Launches no kernel and changes no
  * state: the cpt_adaptive_step after it behaves as without it.  No reference counterpart: a test
  * hook for the tile lists (an addition to the ABI: CPT_ABI_VERSION stays 1). */
+#define CPT_TILE_ORDER_TOPUP 4
 int cpt_debug_read_tile_order(cpt_ctx* ctx, int which, uint32_t* out, size_t capacity, size_t* n);
 /* Device time of the last cpt_render (HIP events on the launch stream); waits for it. */
 int cpt_last_render_ms(cpt_ctx* ctx, float* ms);
