@@ -95,8 +95,12 @@ PROTOTYPES = {
     "cpt_last_filter_ms": (_I, [_P, _P]),
     "cpt_filter_prepare_host": (_I, [_SZ, _P, _P, _P, _P]),
     "cpt_filter_level_host": (_I, [_I, _I, _I, _P, _P, _P, ctypes.c_float, _I, _P]),
+    "cpt_filter_frame_spatial": (_I, [_P, _I, ctypes.c_float, _I]),
+    "cpt_filter_prepare_spatial_host": (_I, [_I, _I, _P, _P, _P, _I, _P, _P]),
+    "cpt_filter_level_id_host": (_I, [_I, _I, _I, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
     "cpt_gbuffer": (_I, [_P, _P, _U32]),
     "cpt_read_gbuffer": (_I, [_P, _P, _P, _P, _P, _SZ]),
+    "cpt_write_gbuffer": (_I, [_P, _P, _P, _P, _P, _SZ]),
     "cpt_trace_rays": (_I, [_P, _SZ, _P, _P, _P, _U32, _P, _P, _P]),
     "cpt_pick": (_I, [_P, _P, _I, _I, _U32, _P, _P]),
     "cpt_last_query_ms": (_I, [_P, _P]),

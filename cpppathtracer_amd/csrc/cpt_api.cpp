@@ -495,6 +495,7 @@ bool PathTracer::EnsureFrame(const MotionalCamera& cam) {
             const int rc = n == 1 ? cpt_set_frame(tiles_[r].ctx, cam.width_, cam.height_, nullptr, 0)
                                   : cpt_set_frame(tiles_[r].ctx, cam.width_, cam.height_, rows.data(), (int)rows.size());
             if (rc != CPT_OK) return Fail("cpt_set_frame", tiles_[r].ctx);
+            accum_cam_set_ = gbuffer_known_ = false;   // a fresh frame: no radiance, no G-buffer
             tiles_[r].rng_ready = false;
         }
         if (frame_ && cpt_set_frame(frame_, cam.width_, cam.height_, nullptr, 0) != CPT_OK) return Fail("cpt_set_frame", frame_);
@@ -517,8 +518,32 @@ bool PathTracer::EnsureFrame(const MotionalCamera& cam) {
 
 // One render of `spp` passes: every tile's launch is queued first (each context's work runs on
 // its own device and stream), then the tiles are gathered into the frame context.
+static MotionalCamera query_camera(const MotionalCamera& cam);
+
+// `cam` as FilterRadianceSpatial's records keep it: the basis computed, the sample index (which no
+// first hit depends on) cleared, so that two copies of one camera compare equal byte for byte.
+static MotionalCamera record_camera(const MotionalCamera& cam) {
+    MotionalCamera c = query_camera(cam);
+    c.cur_sample_idx_ = 0;
+    return c;
+}
+
+// The accumulator now belongs to `cam` (FilterRadianceSpatial).
+void PathTracer::NoteAccumCamera(const MotionalCamera& cam) {
+    accum_cam_ = record_camera(cam);
+    accum_cam_set_ = true;
+}
+
+// The first tile's frame G-buffer now holds `cam`'s first hits in the scene as that tile has it.
+void PathTracer::NoteGBuffer(const MotionalCamera& cam) {
+    gbuffer_cam_ = record_camera(cam);
+    gbuffer_rev_ = tiles_[0].scene_rev;
+    gbuffer_known_ = true;
+}
+
 bool PathTracer::RenderPass(MotionalCamera& cam, int spp, bool accumulate) {
     if (!SyncScene() || !EnsureFrame(cam)) return false;
+    NoteAccumCamera(cam);
     // many passes per pixel: heaviest tiles first (same image, shorter tail)
     // few passes (the DispatchRay loop): heaviest tiles first by the previous pass's work, no pilot
     const uint32_t flags = CPT_RENDER_AUX | (accumulate ? CPT_RENDER_ACCUMULATE : 0u) |
@@ -655,6 +680,7 @@ bool PathTracer::DisplayPassWithHistory(MotionalCamera& cma) {
             loop_history_ = false;
             // (edits another call already brought to the context cannot be captured behind)
             if (tiles_[0].scene_build == prev_scene_build_ && tiles_[0].scene_rev == prev_scene_rev_) {
+                gbuffer_known_ = false;   // the capture traces the frame's G-buffer
                 if (cpt_history_capture(ctx, reinterpret_cast<const cpt_camera*>(&prev_cam_), walk) != CPT_OK)
                     return Fail("cpt_history_capture", ctx);
                 loop_history_ = true;
@@ -672,6 +698,7 @@ bool PathTracer::DisplayPassWithHistory(MotionalCamera& cma) {
             // dropped by a new frame or scene, never captured, or not the previous pass's: restart
             if (!history_is_prev(t0.ctx, carry)) return Fail("cpt_history_info", t0.ctx);
         }
+        if (carry) gbuffer_known_ = false;   // both reprojection calls trace the frame's G-buffer
         if (carry && display_through_edits_) {
             if (cpt_reproject_display_tracked(t0.ctx, reinterpret_cast<const cpt_camera*>(&cma), display_max_history_,
                                               display_plane_tol_, walk) != CPT_OK)
@@ -727,6 +754,7 @@ bool PathTracer::RenderToCount(int target) {
     MotionalCamera cam = camera_->GetCopy();
     std::lock_guard<std::mutex> lk(mu_);
     if (!SyncScene() || !EnsureFrame(cam)) return false;
+    NoteAccumCamera(cam);
     const uint32_t flags = CPT_RENDER_AUX | (ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u);
     const cpt_camera* c = reinterpret_cast<const cpt_camera*>(&cam);
     if (!frame_) {
@@ -809,6 +837,7 @@ bool PathTracer::RenderAdaptive(int min_spp, int max_spp, int batch, float rel_e
     MotionalCamera cma = camera_->GetCopy();
     std::lock_guard<std::mutex> lk(mu_);
     if (!SyncScene() || !EnsureFrame(cma)) return false;
+    NoteAccumCamera(cma);   // for the row tiles too (RenderAdaptiveTiles)
     const uint32_t flags = CPT_RENDER_AUX | (ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) |
                            (max_spp >= 64 ? CPT_SCHEDULE_COST : 0u);
     if (frame_) return RenderAdaptiveTiles(cma, min_spp, max_spp, batch, rel_error, flags, rounds, passes_done);
@@ -837,6 +866,29 @@ bool PathTracer::FilterRadiance(int levels, float sigma_l, int sharpness) {
         return false;
     }
     if (cpt_filter_frame(FrameCtx(), levels, sigma_l, sharpness) != CPT_OK) return Fail("cpt_filter_frame");
+    return true;
+}
+
+bool PathTracer::FilterRadianceSpatial(int levels, float sigma_l, int sharpness) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (tiles_.empty() || width_ == 0 || !accum_cam_set_) {
+        err_ = "FilterRadianceSpatial: Render first";
+        return false;
+    }
+    if (frame_) {
+        err_ = "FilterRadianceSpatial: not available with SetDevices(n > 1), the row tiles own their G-buffers";
+        return false;
+    }
+    cpt_ctx* ctx = tiles_[0].ctx;
+    // the G-buffer the context holds is reused only if it is the accumulator's camera's, in the
+    // scene the context has now
+    if (!gbuffer_known_ || gbuffer_rev_ != tiles_[0].scene_rev || std::memcmp(&gbuffer_cam_, &accum_cam_, sizeof(accum_cam_)) != 0) {
+        gbuffer_known_ = false;
+        if (cpt_gbuffer(ctx, reinterpret_cast<const cpt_camera*>(&accum_cam_), ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK)
+            return Fail("cpt_gbuffer", ctx);
+        NoteGBuffer(accum_cam_);
+    }
+    if (cpt_filter_frame_spatial(ctx, levels, sigma_l, sharpness) != CPT_OK) return Fail("cpt_filter_frame_spatial", ctx);
     return true;
 }
 
@@ -939,9 +991,11 @@ bool PathTracer::ReadGBuffer(std::vector<int32_t>& id, std::vector<float>& t, st
     std::lock_guard<std::mutex> lk(mu_);
     if (!SyncScene() || !EnsureFrame(cma)) return false;
     const uint32_t flags = ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u;
+    gbuffer_known_ = false;
     for (Tile& tile : tiles_)
         if (cpt_gbuffer(tile.ctx, reinterpret_cast<const cpt_camera*>(&cma), flags) != CPT_OK)
             return Fail("cpt_gbuffer", tile.ctx);
+    NoteGBuffer(cma);
     const size_t w = (size_t)width_, npix = w * height_;
     id.resize(npix);
     t.resize(npix);
@@ -993,6 +1047,8 @@ bool PathTracer::Reproject(const MotionalCamera& from, int max_history, float pl
                             plane_tol, ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK ||
         cpt_synchronize(ctx) != CPT_OK)
         return Fail("cpt_reproject_accum", ctx);
+    NoteAccumCamera(to);
+    NoteGBuffer(to);
     loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
     return true;
 }
@@ -1011,8 +1067,10 @@ bool PathTracer::CaptureHistory() {
         return false;
     }
     cpt_ctx* ctx = tiles_[0].ctx;
+    gbuffer_known_ = false;
     if (cpt_history_capture(ctx, reinterpret_cast<const cpt_camera*>(&cam), ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK)
         return Fail("cpt_history_capture", ctx);
+    NoteGBuffer(cam);
     loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
     return true;
 }
@@ -1034,6 +1092,8 @@ bool PathTracer::ReprojectTracked(int max_history, float plane_tol) {
                                     ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK ||
         cpt_synchronize(ctx) != CPT_OK)
         return Fail("cpt_reproject_accum_tracked", ctx);
+    NoteAccumCamera(to);
+    NoteGBuffer(to);
     loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
     return true;
 }

@@ -1,6 +1,7 @@
 // cpt_capi_filter.cpp — the C-ABI's variance-guided a-trous filter of an adaptive render's final
 // frame (include/cpt.h): cpt_filter_frame and its read-outs, the moments'
-// checkpoint pair, and the host-only hooks on the filter's arithmetic.  The kernels are
+// checkpoint pair, and the host-only hooks on the filter's arithmetic; and the same filter for frames
+// without moments (§25): cpt_filter_frame_spatial and its two host hooks.  The kernels are
 // cpt_filter.hip's; the arithmetic is cpt_filter.hpp's on both sides.
 #include <hip/hip_runtime.h>
 
@@ -50,6 +51,40 @@ int cpt_filter_frame(cpt_ctx* c, int levels, float sigma_l, int normal_sharpness
     for (int l = 0; l < levels; ++l)
         HIP_TRY(c, cpt::launch_filter_level(f.filter.d_plane[l & 1], f.d_normal, f.filter.d_ok, f.filter.d_plane[(l + 1) & 1], c->width, c->height,
                                            1 << l, sigma_l * sigma_l, normal_sharpness_log2, s));
+    HIP_TRY(c, hipEventRecord(c->t_filter.t1, s));
+    c->t_filter.recorded = true;
+    f.filter.result = levels & 1;
+    return CPT_OK;
+}
+
+int cpt_filter_frame_spatial(cpt_ctx* c, int levels, float sigma_l, int normal_sharpness_log2) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    if (levels < 0 || levels > flt::MAX_LEVELS || !args_ok(sigma_l, normal_sharpness_log2))
+        return fail(c, CPT_ERR_INVALID_ARG,
+                    "cpt_filter_frame_spatial: levels %d (0..8), sigma_l %g (finite, >= 0), normal_sharpness_log2 %d (0..10)", levels,
+                    (double)sigma_l, normal_sharpness_log2);
+    CPT_REFUSE_PENDING(c, "cpt_filter_frame_spatial");
+    Frame& f = c->frame;
+    if (!f.set || c->n_rows != c->height) return fail(c, CPT_ERR_STATE, "cpt_filter_frame_spatial: needs a full frame");
+    for (int y = 0; y < c->height; ++y)
+        if (c->rows_h[y] != y) return fail(c, CPT_ERR_STATE, "cpt_filter_frame_spatial: needs rows 0..height-1 in order");
+    const size_t npix = c->npix();
+    const GBufferState& g = f.gbuffer;
+    if (!g.valid || g.d_id.capacity() < npix || g.d_normal.capacity() < 3 * npix)
+        return fail(c, CPT_ERR_STATE, "cpt_filter_frame_spatial: no G-buffer (cpt_gbuffer, a reprojection or cpt_write_gbuffer first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = f.filter.d_plane[0].ensure(c, npix)) != CPT_OK || (rc = f.filter.d_plane[1].ensure(c, npix)) != CPT_OK ||
+        (rc = f.filter.d_ok.ensure(c, npix)) != CPT_OK)
+        return rc;
+    f.filter.result = -1;
+    hipStream_t s = c->stream();
+    HIP_TRY(c, hipEventRecord(c->t_filter.t0, s));
+    HIP_TRY(c, cpt::launch_filter_prepare_spatial(f.d_accum, g.d_id, g.d_normal, c->width, c->height, normal_sharpness_log2,
+                                                  f.filter.d_plane[0], f.filter.d_ok, s));
+    for (int l = 0; l < levels; ++l)
+        HIP_TRY(c, cpt::launch_filter_level_id(f.filter.d_plane[l & 1], g.d_normal, g.d_id, f.filter.d_ok, f.filter.d_plane[(l + 1) & 1],
+                                              c->width, c->height, 1 << l, sigma_l * sigma_l, normal_sharpness_log2, s));
     HIP_TRY(c, hipEventRecord(c->t_filter.t1, s));
     c->t_filter.recorded = true;
     f.filter.result = levels & 1;
@@ -140,6 +175,52 @@ int cpt_filter_level_host(int width, int height, int step, const float* in_rgbv,
             out[(size_t)y * width + x] = src.valid(x, y) ? flt::level_pixel(src, x, y, width, height, step, sigma_l * sigma_l,
                                                                             normal_sharpness_log2)
                                                          : src.px(x, y);
+    return CPT_OK;
+}
+
+int cpt_filter_prepare_spatial_host(int width, int height, const float* accum_rgba, const int32_t* id, const float* normal3,
+                                    int normal_sharpness_log2, float* out_rgbv, uint8_t* out_valid) {
+    if (width <= 0 || height <= 0 || !accum_rgba || !id || !normal3 || !out_rgbv || !out_valid || normal_sharpness_log2 < 0 ||
+        normal_sharpness_log2 > flt::MAX_SHARPNESS_LOG2)
+        return CPT_ERR_INVALID_ARG;
+    const size_t npix = (size_t)width * height;
+    std::vector<float> l(npix), n(npix);
+    std::vector<uint8_t> b(npix);
+    for (size_t i = 0; i < npix; ++i) {
+        const float* S = accum_rgba + 4 * i;
+        flt::Px c;
+        b[i] = flt::spatial_base(S[0], S[1], S[2], S[3], c) ? 1 : 0;
+        l[i] = flt::luma(c);
+        n[i] = S[3];
+    }
+    const flt::SpatialPlaneSrc src{l.data(), n.data(), b.data(), id, normal3, width};
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const size_t i = (size_t)y * width + x;
+            const float* S = accum_rgba + 4 * i;
+            flt::Px c;
+            out_valid[i] = flt::prepare_spatial(src, x, y, width, height, S[0], S[1], S[2], S[3], normal_sharpness_log2, c) ? 1 : 0;
+            out_rgbv[4 * i] = c.r;
+            out_rgbv[4 * i + 1] = c.g;
+            out_rgbv[4 * i + 2] = c.b;
+            out_rgbv[4 * i + 3] = c.v;
+        }
+    return CPT_OK;
+}
+
+int cpt_filter_level_id_host(int width, int height, int step, const float* in_rgbv, const float* normal3, const int32_t* id,
+                             const uint8_t* valid, float sigma_l, int normal_sharpness_log2, float* out_rgbv) {
+    if (width <= 0 || height <= 0 || step < 1 || step > (1 << (flt::MAX_LEVELS - 1)) || !in_rgbv || !normal3 || !id || !valid ||
+        !out_rgbv || in_rgbv == out_rgbv || !args_ok(sigma_l, normal_sharpness_log2))
+        return CPT_ERR_INVALID_ARG;
+    const flt::PlaneIdSrc src{{reinterpret_cast<const flt::Px*>(in_rgbv), normal3, valid, width}, id};
+    flt::Px* out = reinterpret_cast<flt::Px*>(out_rgbv);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x)
+            out[(size_t)y * width + x] =
+                src.valid(x, y) ? flt::level_pixel<flt::PlaneIdSrc, true>(src, x, y, width, height, step, sigma_l * sigma_l,
+                                                                          normal_sharpness_log2)
+                                : src.px(x, y);
     return CPT_OK;
 }
 

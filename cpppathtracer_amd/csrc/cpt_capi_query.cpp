@@ -1,6 +1,7 @@
-// cpt_capi_query.cpp — the C-ABI's first-hit queries (include/cpt.h): cpt_gbuffer
-// and its read-out, cpt_trace_rays, cpt_pick and their timing.  The kernel is cpt_query.hip's; it
-// reads the scene and the camera and writes only the buffers named here.
+// cpt_capi_query.cpp — the C-ABI's first-hit queries (include/cpt.h): cpt_gbuffer,
+// its read-out and its checkpoint writer (cpt_write_gbuffer), cpt_trace_rays, cpt_pick and their
+// timing.  The kernel is cpt_query.hip's; it reads the scene and the camera and writes only the
+// buffers named here.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -83,6 +84,38 @@ int cpt_read_gbuffer(cpt_ctx* c, int32_t* id, float* t, float* normal3, float* a
     if (t) HIP_TRY(c, hipMemcpy(t, g.d_t, n * sizeof(float), hipMemcpyDeviceToHost));
     if (normal3) HIP_TRY(c, hipMemcpy(normal3, g.d_normal, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
     if (albedo3) HIP_TRY(c, hipMemcpy(albedo3, g.d_albedo, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
+    return CPT_OK;
+}
+
+int cpt_write_gbuffer(cpt_ctx* c, const int32_t* id, const float* t, const float* normal3, const float* albedo3,
+                      size_t count_pixels) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    if (!c->frame.set) return fail(c, CPT_ERR_STATE, "cpt_write_gbuffer: no frame");
+    const size_t n = c->npix();
+    if (count_pixels < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_write_gbuffer: %zu < %zu pixels", count_pixels, n);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    GBufferState& g = c->frame.gbuffer;
+    // a plane that was never written starts as zeros: one that is new here, or all four when no
+    // G-buffer is valid yet
+    const bool fresh[4] = {!g.valid || g.d_id.capacity() < n, !g.valid || g.d_t.capacity() < n,
+                           !g.valid || g.d_normal.capacity() < 3 * n, !g.valid || g.d_albedo.capacity() < 3 * n};
+    int rc;
+    if ((rc = g.d_id.ensure(c, n)) != CPT_OK || (rc = g.d_t.ensure(c, n)) != CPT_OK ||
+        (rc = g.d_normal.ensure(c, 3 * n)) != CPT_OK || (rc = g.d_albedo.ensure(c, 3 * n)) != CPT_OK)
+        return rc;
+    if (n) {
+        if (id) HIP_TRY(c, hipMemcpy(g.d_id, id, n * sizeof(int32_t), hipMemcpyHostToDevice));
+        else if (fresh[0]) HIP_TRY(c, hipMemsetAsync(g.d_id, 0, n * sizeof(int32_t), c->stream()));
+        if (t) HIP_TRY(c, hipMemcpy(g.d_t, t, n * sizeof(float), hipMemcpyHostToDevice));
+        else if (fresh[1]) HIP_TRY(c, hipMemsetAsync(g.d_t, 0, n * sizeof(float), c->stream()));
+        if (normal3) HIP_TRY(c, hipMemcpy(g.d_normal, normal3, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+        else if (fresh[2]) HIP_TRY(c, hipMemsetAsync(g.d_normal, 0, 3 * n * sizeof(float), c->stream()));
+        if (albedo3) HIP_TRY(c, hipMemcpy(g.d_albedo, albedo3, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+        else if (fresh[3]) HIP_TRY(c, hipMemsetAsync(g.d_albedo, 0, 3 * n * sizeof(float), c->stream()));
+        HIP_TRY(c, hipStreamSynchronize(c->stream()));   // the fills: a later copy into the plane must not race them
+    }
+    g.valid = true;
     return CPT_OK;
 }
 

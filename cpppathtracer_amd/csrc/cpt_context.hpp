@@ -133,19 +133,20 @@ struct AdaptiveState {
     }
 };
 
-// The a-trous filter (cpt_capi_filter.cpp; allocated on the frame's first cpt_filter_frame).
+// The a-trous filter (cpt_capi_filter.cpp; allocated on the frame's first cpt_filter_frame or
+// cpt_filter_frame_spatial, which share the planes).
 struct FilterState {
     DevBuf<float4> d_plane[2];   // the levels ping-pong between them (rgb + variance of the mean)
     DevBuf<uint8_t> d_ok;        // each pixel's validity
     int result = -1;             // the plane that holds the last call's result (-1: no call yet)
 };
 
-// The G-buffer (cpt_capi_query.cpp; allocated on the frame's first cpt_gbuffer).
+// The G-buffer (cpt_capi_query.cpp; allocated on the frame's first cpt_gbuffer or cpt_write_gbuffer).
 struct GBufferState {
     DevBuf<int32_t> d_id;               // object index per pixel (-1: miss)
     DevBuf<float> d_t;                  // hit distance
     DevBuf<float> d_normal, d_albedo;   // [npix][3] each
-    bool valid = false;                 // a cpt_gbuffer has been queued since cpt_set_frame
+    bool valid = false;                 // a cpt_gbuffer has been queued, or a cpt_write_gbuffer made, since cpt_set_frame
 };
 
 // The reprojection (cpt_capi_reproject.cpp; allocated on the frame's first cpt_reproject_accum or

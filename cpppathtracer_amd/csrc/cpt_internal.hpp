@@ -198,6 +198,14 @@ hipError_t launch_filter_prepare(const float4* accum, const float* stat, size_t 
                                  hipStream_t stream);
 hipError_t launch_filter_level(const float4* in, const float* normal3, const uint8_t* ok, float4* out, int width, int height,
                                int step, float sig2, int sharpness_log2, hipStream_t stream);
+// The same filter without moments (cpt_filter_frame_spatial).
+// launch_filter_prepare_spatial: plane and ok from the accumulator and the G-buffer's id and normal
+// planes, the variance from the 7x7 window.  launch_filter_level_id: launch_filter_level with the
+// stop at object boundaries, a tap of another `id` being skipped.
+hipError_t launch_filter_prepare_spatial(const float4* accum, const int32_t* id, const float* normal3, int width, int height,
+                                         int sharpness_log2, float4* plane, uint8_t* ok, hipStream_t stream);
+hipError_t launch_filter_level_id(const float4* in, const float* normal3, const int32_t* id, const uint8_t* ok, float4* out,
+                                  int width, int height, int step, float sig2, int sharpness_log2, hipStream_t stream);
 
 // Wavefront path state (cpt_wavefront.hip): SoA float4 arrays indexed by QUEUE SLOT + queues.
 // The carried state is double-buffered: bounce b reads buffer b & 1 at its queue slot and shade

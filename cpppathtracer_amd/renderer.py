@@ -371,8 +371,18 @@ class Renderer:
         about sigma_l standard errors.  Asynchronous; read_filtered waits."""
         self._check(self._L.cpt_filter_frame(self._ctx, int(levels), ctypes.c_float(sigma_l), int(normal_sharpness_log2)))
 
+    def filter_frame_spatial(self, levels=3, sigma_l=2.0, normal_sharpness_log2=3):
+        """cpt_filter_frame_spatial: filter_frame for a frame without moments (a plain render, a
+        reprojected or topped-up frame).  Level 0's variance is estimated from each pixel's 7x7
+        window, count-weighted, within its object; the levels are guided by the G-buffer's normals
+        and stop at its object boundaries.  Needs a full frame and a valid G-buffer OF THE CAMERA
+        THE ACCUMULATOR BELONGS TO: a reprojection leaves it, after a plain render call gbuffer(cam)
+        first.  Asynchronous; read_filtered and last_filter_ms serve both filters."""
+        self._check(self._L.cpt_filter_frame_spatial(self._ctx, int(levels), ctypes.c_float(sigma_l),
+                                                     int(normal_sharpness_log2)))
+
     def read_filtered(self):
-        """The last filter_frame's result (cpt_read_filtered): (rgb [npix, 3], variance of the
+        """The last filter_frame's or filter_frame_spatial's result (cpt_read_filtered): (rgb [npix, 3], variance of the
         filtered mean [npix]) float32."""
         rgb = np.zeros((self.npix, 3), dtype=np.float32)
         var = np.zeros(self.npix, dtype=np.float32)
@@ -403,6 +413,22 @@ class Renderer:
         self._check(self._L.cpt_read_gbuffer(self._ctx, _p(out["id"]), _p(out["t"]), _p(out["normal"]), _p(out["albedo"]),
                                              self.npix))
         return out
+
+    def write_gbuffer(self, id=None, t=None, normal=None, albedo=None):
+        """Restore the G-buffer's planes from host copies (cpt_write_gbuffer; read_gbuffer's shapes)
+        and make it valid.  A plane given as None is left as it is (zeros if never written)."""
+        def plane(a, dtype, shape, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if a.size != int(np.prod(shape)):
+                raise ValueError(f"write_gbuffer: {name} of {a.size} values, expected shape {shape}")
+            return a.reshape(shape)
+        i = plane(id, np.int32, (self.npix,), "id")
+        d = plane(t, np.float32, (self.npix,), "t")
+        n = plane(normal, np.float32, (self.npix, 3), "normal")
+        k = plane(albedo, np.float32, (self.npix, 3), "albedo")
+        self._check(self._L.cpt_write_gbuffer(self._ctx, _p(i), _p(d), _p(n), _p(k), self.npix))
 
     def trace_rays(self, origins, dirs, tmin=None, flags=0):
         """cpt_trace_rays: the first hit of each ray (origins, dirs [n, 3]; tmin [n] or None = 0);

@@ -6,7 +6,15 @@
 //                [--texture file.ppm|file.cptex] [--dump-scene objects.bin] [--devices N]
 //                [--objects N] [--animate K [--animate-step X]] [--pick X,Y] [--orbit N [--reproject]]
 //                [--orbit N [--animate K] --display-reproject on|off|edits --bgra frame.bin]
-//                [--animate K --reproject] [--fill T]
+//                [--animate K --reproject] [--fill T] [--filter-spatial [LEVELS] [--look-aside]]
+//
+// --filter-spatial [LEVELS] (without --adaptive: with plain --spp, and with --orbit N --reproject
+// [--fill T]): the last frame is filtered without moments, its variance estimated from each pixel's
+// neighbourhood and the levels guided by the G-buffer (PathTracer::FilterRadianceSpatial, DESIGN.md
+// §25; 3 levels by default), and --pfm gets the filtered image.  With --look-aside the camera then
+// turns one degree, PathTracer::ReadGBuffer is read there (an editor's overlay at the new view: the
+// context's G-buffer is now that camera's) and the frame is filtered again: the radiance still
+// belongs to the camera it was rendered with, so the second result, which --pfm gets, is the first's.
 //
 // --fill T (with --orbit N --reproject, and with --animate K --reproject): each frame after the
 // first is topped up to T passes per pixel (PathTracer::RenderToCount) instead of
@@ -182,6 +190,8 @@ int main(int argc, char** argv) {
     // (PathTracer::FilterRadiance, 5 levels by default); --pfm then gets the filtered image
     int filter_levels = -1;
     int orbit = 0;
+    int filter_spatial = -1;   // --filter-spatial [LEVELS]: FilterRadianceSpatial on the last frame (-1: off)
+    bool look_aside = false;   // --look-aside (with --filter-spatial): ReadGBuffer at a turned camera, then filter again
     int fill = 0;   // --fill T: frames after the first are topped up to T passes (0: --spp uniform passes)
     float animate_step = 0.75f;
     bool reproject = false;
@@ -192,6 +202,17 @@ int main(int argc, char** argv) {
             const bool has_value = i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0;
             filter_levels = has_value ? std::stoi(argv[i + 1]) : 5;
             if (!has_value) --i;
+            continue;
+        }
+        if (k == "--filter-spatial") {
+            const bool has_value = i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0;
+            filter_spatial = has_value ? std::stoi(argv[i + 1]) : 3;
+            if (!has_value) --i;
+            continue;
+        }
+        if (k == "--look-aside") {
+            look_aside = true;
+            --i;
             continue;
         }
         if (k == "--reproject") {
@@ -290,6 +311,14 @@ int main(int argc, char** argv) {
 
     if (fill != 0 && (fill < 1 || !reproject || (orbit <= 0 && animate <= 0))) {
         fprintf(stderr, "--fill wants T >= 1 and --reproject with --orbit N or --animate K\n");
+        return 2;
+    }
+    if (filter_spatial >= 0 && (adaptive >= 0.f || animate > 0 || !display_reproject.empty() || (orbit > 0 && !reproject))) {
+        fprintf(stderr, "--filter-spatial wants plain --spp or --orbit N --reproject [--fill T], without --adaptive\n");
+        return 2;
+    }
+    if (look_aside && filter_spatial < 0) {
+        fprintf(stderr, "--look-aside wants --filter-spatial\n");
         return 2;
     }
     if (!display_reproject.empty()) {
@@ -429,7 +458,21 @@ int main(int argc, char** argv) {
         std::ofstream f(out, std::ios::binary);
         f.write(reinterpret_cast<const char*>(rgb.data()), (std::streamsize)(rgb.size() * sizeof(float)));
     }
-    const bool filtered = adaptive >= 0.f && filter_levels >= 0 && animate == 0;
+    if (filter_spatial >= 0) {
+        if (!tracer.FilterRadianceSpatial(filter_spatial)) { fprintf(stderr, "FilterRadianceSpatial: %s\n", tracer.LastError().c_str()); return 1; }
+        printf("filtered without moments: %d levels\n", filter_spatial);
+        if (look_aside) {
+            const float c = 0.99984770f, s = 0.01745241f;
+            const float dx = cam->origin_.x - cam->look_at_.x, dz = cam->origin_.z - cam->look_at_.z;
+            cam->SetOrigin(cam->look_at_.x + (c * dx + s * dz), cam->origin_.y, cam->look_at_.z + (c * dz - s * dx));
+            std::vector<int32_t> id;
+            std::vector<float> t, normal3, albedo3;
+            if (!tracer.ReadGBuffer(id, t, normal3, albedo3)) { fprintf(stderr, "ReadGBuffer: %s\n", tracer.LastError().c_str()); return 1; }
+            if (!tracer.FilterRadianceSpatial(filter_spatial)) { fprintf(stderr, "FilterRadianceSpatial: %s\n", tracer.LastError().c_str()); return 1; }
+            printf("looked aside (G-buffer at the turned camera) and filtered again\n");
+        }
+    }
+    const bool filtered = filter_spatial >= 0 || (adaptive >= 0.f && filter_levels >= 0 && animate == 0);
     if (!pfm.empty() && !(filtered ? tracer.SaveFilteredPFM(pfm) : tracer.SaveRadiancePFM(pfm))) { fprintf(stderr, "%s\n", tracer.LastError().c_str()); return 1; }
     return 0;
 }

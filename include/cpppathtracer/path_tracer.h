@@ -10,7 +10,7 @@
 //   SetCamera / GetCamera
 // Additions the headless configs need (the reference has no setters for these):
 //   SetMaxRecursionDepth, SetSeed, SetDevice, SetDevices (row tiling over several GPUs),
-//   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance,
+//   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance, FilterRadianceSpatial,
 //   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
 //   Reproject, CaptureHistory, ReprojectTracked, RenderToCount, SetDisplayReprojection, GetStats,
 //   Stop.
@@ -85,6 +85,16 @@ public:
     // about sigma_l standard errors of the pixel's mean.  The radiance accumulator is not
     // changed; ReadFiltered / SaveFilteredPFM read the result (rgb float[width*height*3]).
     bool FilterRadiance(int levels = 5, float sigma_l = 1.0f, int sharpness = 7);
+    // The same filter for a frame without moments: what Render, Reproject / ReprojectTracked and
+    // RenderToCount leave (cpt_filter_frame_spatial).  The variance comes from each
+    // pixel's 7x7 window and the levels are guided by the G-buffer of the camera the radiance
+    // belongs to, the one of the last Render / RenderAdaptive / RenderToCount / Reproject*.  A
+    // reprojection leaves that G-buffer; where the context holds another (none yet, one that
+    // ReadGBuffer or CaptureHistory traced at a camera moved since, one of the scene before an
+    // edit) it is traced here first, so the current camera may look elsewhere meanwhile.
+    // ReadFiltered / SaveFilteredPFM read the result.  Not available with SetDevices(n > 1)
+    // (false, LastError).
+    bool FilterRadianceSpatial(int levels = 3, float sigma_l = 2.0f, int sharpness = 3);
     bool ReadFiltered(std::vector<float>& rgb);
     bool SaveFilteredPFM(const std::string& path);
     // Per-pixel mean radiance, rgb float[width*height*3] (row-major, y down).
@@ -211,6 +221,16 @@ private:
     uint64_t loop_history_rev_ = 0;
     int display_max_history_ = 32;
     float display_plane_tol_ = 1e-2f;
+    // FilterRadianceSpatial compares two records.  The camera the radiance belongs to: every
+    // call that renders into or reprojects the accumulator notes it (NoteAccumCamera).  And what the
+    // first tile's frame G-buffer holds, a camera in a scene revision: every call that writes that
+    // G-buffer notes it (NoteGBuffer) or, where it is not worth following, forgets it
+    // (gbuffer_known_ = false), as a new frame does.
+    bool accum_cam_set_ = false, gbuffer_known_ = false;
+    MotionalCamera accum_cam_, gbuffer_cam_;
+    uint64_t gbuffer_rev_ = 0;
+    void NoteAccumCamera(const MotionalCamera& cam);
+    void NoteGBuffer(const MotionalCamera& cam);
     bool prev_pass_ = false;
     MotionalCamera prev_cam_;
     uint64_t prev_scene_build_ = 0, prev_scene_rev_ = 0;

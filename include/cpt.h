@@ -410,6 +410,34 @@ int cpt_filter_prepare_host(size_t npix, const float* accum_rgba, const float* m
                             uint8_t* out_valid);
 int cpt_filter_level_host(int width, int height, int step, const float* in_rgbv, const float* normal3, const uint8_t* valid,
                           float sigma_l, int normal_sharpness_log2, float* out_rgbv);
+/* The same filter for a frame without moments: a plain cpt_render, a reprojected frame, one that
+ * cpt_render_to_count topped up (an addition).  It reads the accumulator and the
+ * frame's G-buffer (id and normal planes) and needs neither moments nor aux normals.  Level 0's
+ * variance of the mean is spatial: over the 7x7 window of a pixel, among the pixels of the same
+ * object id that hold a finite mean, the count-weighted variance of the luminance, each tap weighted
+ * by the normals' agreement as above, scaled to the pixel's own count (0 for a pixel alone in its
+ * window).  A pixel without a pass or with a value that is not finite is left as it is and is no
+ * tap of another pixel.  The levels are cpt_filter_frame's, guided by the G-buffer's normals, with
+ * one more stop: a tap of another object id is skipped, in the 3x3 variance prefilter too.
+ * Argument ranges and CPT_ERR_INVALID_ARG as cpt_filter_frame.  CPT_ERR_STATE: no frame, a frame
+ * that is not full (rows != NULL), no valid G-buffer, or an adaptive render pending.
+ * THE G-BUFFER MUST BE THE ONE OF THE CAMERA THE ACCUMULATOR NOW BELONGS TO.  After any
+ * cpt_reproject_* call it is (they leave `to`'s, and cpt_render_to_count keeps it); after a plain
+ * cpt_render the caller runs cpt_gbuffer at the render's camera first.  The call cannot check this.
+ * Writes only the filter's own planes (cpt_read_filtered and cpt_last_filter_ms serve both filters;
+ * a call that fails its checks leaves an earlier result readable).  Asynchronous, on the context's
+ * stream; no allocation after the frame's first filter call.  Defaults in the wrappers: 3 levels,
+ * sigma_l 2, sharpness 3 (the sweep behind them). */
+int cpt_filter_frame_spatial(cpt_ctx* ctx, int levels, float sigma_l, int normal_sharpness_log2);
+/* HOST ONLY, no GPU: the functions cpt_filter_frame_spatial's kernels run.
+ * cpt_filter_prepare_spatial_host: level 0 of a width x height frame from an accumulator [npix][4]
+ * and the G-buffer's id [npix] and normal3 [npix][3] into out_rgbv and out_valid, as
+ * cpt_filter_prepare_host's.  cpt_filter_level_id_host: cpt_filter_level_host with the stop at
+ * object boundaries of `id` [npix]. */
+int cpt_filter_prepare_spatial_host(int width, int height, const float* accum_rgba, const int32_t* id, const float* normal3,
+                                    int normal_sharpness_log2, float* out_rgbv, uint8_t* out_valid);
+int cpt_filter_level_id_host(int width, int height, int step, const float* in_rgbv, const float* normal3, const int32_t* id,
+                             const uint8_t* valid, float sigma_l, int normal_sharpness_log2, float* out_rgbv);
 /* First-hit queries (additions: the reference has no counterpart; its only first-hit data are the
  * normal and the constant depth 1e30 that SamplePixel writes, path_tracer.cu:172-174, and nothing
  * in it names the object a ray hits).  All of them walk SceneBVH::TraceRay
@@ -436,6 +464,14 @@ int cpt_gbuffer(cpt_ctx* ctx, const cpt_camera* cam, uint32_t flags);
  * [n_rows*width], normal3 and albedo3 [n_rows*width][3]; any may be NULL.  capacity_pixels below
  * n_rows*width: CPT_ERR_INVALID_ARG, nothing written.  Waits. */
 int cpt_read_gbuffer(cpt_ctx* ctx, int32_t* id, float* t, float* normal3, float* albedo3, size_t capacity_pixels);
+/* The other half, with cpt_write_accum, cpt_write_rng, cpt_write_aux and cpt_write_moments the
+ * checkpoint of a session: restores the G-buffer's planes from host copies of count_pixels pixels
+ * each and makes the G-buffer valid (cpt_read_gbuffer and cpt_filter_frame_spatial then work).  A
+ * NULL plane is left as it is, and is zero if it was never written.  Needs a frame (CPT_ERR_STATE);
+ * count_pixels below n_rows*width: CPT_ERR_INVALID_ARG, nothing written.  Waits for the stream
+ * first, as cpt_write_moments does. */
+int cpt_write_gbuffer(cpt_ctx* ctx, const int32_t* id, const float* t, const float* normal3, const float* albedo3,
+                      size_t count_pixels);
 /* n rays from host arrays origin3 / dir3 [n][3] and tmin [n] (NULL: 0 for every ray) into the host
  * arrays id [n], t [n] and normal3 [n][3].  The direction is used as given, not normalised, as
  * TraceRay does (t is in units of its length; a miss's normal is -dir as given); tmax is 1e30.
