@@ -49,6 +49,23 @@ int fail(cpt_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
+int require_full_frame(cpt_ctx* c, const char* who) {
+    if (!c->frame.set || c->n_rows != c->height) return fail(c, CPT_ERR_STATE, "%s: needs a full frame", who);
+    for (int y = 0; y < c->height; ++y)
+        if (c->rows_h[y] != y) return fail(c, CPT_ERR_STATE, "%s: needs rows 0..height-1 in order", who);
+    return CPT_OK;
+}
+
+int last_span_ms(cpt_ctx* c, TimedSpan cpt_ctx::*span, float* ms, const char* nothing_yet) {
+    if (!c || !ms) return CPT_ERR_INVALID_ARG;
+    const TimedSpan& t = c->*span;
+    if (!t.recorded) return fail(c, CPT_ERR_STATE, "%s", nothing_yet);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(t.t1));
+    HIP_TRY(c, hipEventElapsedTime(ms, t.t0, t.t1));
+    return CPT_OK;
+}
+
 // The kernels' sticky error word (KParams::error, CPT_DEVERR_*): read after the context's
 // stream has drained; a set word is cleared and reported once, like a sticky HIP error.
 // Both the read and the clear run on the context's own stream (a blocking hipMemcpy would

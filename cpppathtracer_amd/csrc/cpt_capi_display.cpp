@@ -109,9 +109,7 @@ int DisplayBand::fill_count(cpt_ctx* c) {
 // the launch region is empty (the host frame is zeroed, nothing is launched).
 static int full_frame_display(cpt_ctx* c, const char* who, uint8_t* bgra_host, bool* launch) {
     *launch = false;
-    if (!c->frame.set || c->n_rows != c->height) return fail(c, CPT_ERR_STATE, "%s: needs a full frame", who);
-    for (int y = 0; y < c->height; ++y)
-        if (c->rows_h[y] != y) return fail(c, CPT_ERR_STATE, "%s: needs rows 0..height-1 in order", who);
+    if (int rc = require_full_frame(c, who)) return rc;
     if (16 * (c->width / 16) == 0 || 16 * (c->height / 16) == 0) {   // nothing is launched; the frame stays 0
         if (bgra_host) std::memset(bgra_host, 0, (size_t)c->width * c->height * 4);
         return CPT_OK;
@@ -123,12 +121,7 @@ static int full_frame_display(cpt_ctx* c, const char* who, uint8_t* bgra_host, b
 extern "C" {
 
 int cpt_last_display_ms(cpt_ctx* c, float* ms) {
-    if (!c || !ms) return CPT_ERR_INVALID_ARG;
-    if (!c->t_display.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_display_ms: no display frame yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->t_display.t1));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->t_display.t0, c->t_display.t1));
-    return CPT_OK;
+    return last_span_ms(c, &cpt_ctx::t_display, ms, "cpt_last_display_ms: no display frame yet");
 }
 
 int cpt_denoise_mix(cpt_ctx* c, uint32_t cur_sample_idx, uint8_t* bgra_host) {

@@ -19,76 +19,66 @@ bool args_ok(float sigma_l, int sharpness_log2) {
     return flt::finite(sigma_l) && sigma_l >= 0.f && sharpness_log2 >= 0 && sharpness_log2 <= flt::MAX_SHARPNESS_LOG2;
 }
 
+// cpt_filter_frame and, `spatial`, cpt_filter_frame_spatial: they differ in the guides they need
+// (the moments and the frame's normals, or the G-buffer) and in the kernels those feed.
+int filter_frame(cpt_ctx* c, const char* who, bool spatial, int levels, float sigma_l, int normal_sharpness_log2) {
+    if (!c) return CPT_ERR_INVALID_ARG;
+    if (levels < 0 || levels > flt::MAX_LEVELS || !args_ok(sigma_l, normal_sharpness_log2))
+        return fail(c, CPT_ERR_INVALID_ARG, "%s: levels %d (0..8), sigma_l %g (finite, >= 0), normal_sharpness_log2 %d (0..10)", who,
+                    levels, (double)sigma_l, normal_sharpness_log2);
+    CPT_REFUSE_PENDING(c, who);
+    if (int rc = require_full_frame(c, who)) return rc;
+    Frame& f = c->frame;
+    const GBufferState& g = f.gbuffer;
+    const size_t npix = c->npix();
+    if (spatial) {
+        if (!g.valid || g.d_id.capacity() < npix || g.d_normal.capacity() < 3 * npix)
+            return fail(c, CPT_ERR_STATE, "%s: no G-buffer (cpt_gbuffer, a reprojection or cpt_write_gbuffer first)", who);
+    } else {
+        if (!f.adaptive.has_result(npix))
+            return fail(c, CPT_ERR_STATE, "%s: no moments (cpt_render_adaptive or cpt_write_moments first)", who);
+        if (f.d_normal.capacity() < 3 * npix)
+            return fail(c, CPT_ERR_STATE, "%s: no normals (render with CPT_RENDER_AUX or cpt_write_aux first)", who);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    FilterState& ft = f.filter;
+    int rc;
+    if ((rc = ft.d_plane[0].ensure(c, npix)) != CPT_OK || (rc = ft.d_plane[1].ensure(c, npix)) != CPT_OK ||
+        (rc = ft.d_ok.ensure(c, npix)) != CPT_OK)
+        return rc;
+    ft.result = -1;
+    hipStream_t s = c->stream();
+    const float sigma2 = sigma_l * sigma_l;
+    HIP_TRY(c, hipEventRecord(c->t_filter.t0, s));
+    if (spatial)
+        HIP_TRY(c, cpt::launch_filter_prepare_spatial(f.d_accum, g.d_id, g.d_normal, c->width, c->height, normal_sharpness_log2,
+                                                      ft.d_plane[0], ft.d_ok, s));
+    else
+        HIP_TRY(c, cpt::launch_filter_prepare(f.d_accum, f.adaptive.d_stat, npix, ft.d_plane[0], ft.d_ok, s));
+    for (int l = 0; l < levels; ++l) {
+        if (spatial)
+            HIP_TRY(c, cpt::launch_filter_level_id(ft.d_plane[l & 1], g.d_normal, g.d_id, ft.d_ok, ft.d_plane[(l + 1) & 1], c->width,
+                                                  c->height, 1 << l, sigma2, normal_sharpness_log2, s));
+        else
+            HIP_TRY(c, cpt::launch_filter_level(ft.d_plane[l & 1], f.d_normal, ft.d_ok, ft.d_plane[(l + 1) & 1], c->width, c->height,
+                                               1 << l, sigma2, normal_sharpness_log2, s));
+    }
+    HIP_TRY(c, hipEventRecord(c->t_filter.t1, s));
+    c->t_filter.recorded = true;
+    ft.result = levels & 1;
+    return CPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int cpt_filter_frame(cpt_ctx* c, int levels, float sigma_l, int normal_sharpness_log2) {
-    if (!c) return CPT_ERR_INVALID_ARG;
-    if (levels < 0 || levels > flt::MAX_LEVELS || !args_ok(sigma_l, normal_sharpness_log2))
-        return fail(c, CPT_ERR_INVALID_ARG,
-                    "cpt_filter_frame: levels %d (0..8), sigma_l %g (finite, >= 0), normal_sharpness_log2 %d (0..10)", levels,
-                    (double)sigma_l, normal_sharpness_log2);
-    CPT_REFUSE_PENDING(c, "cpt_filter_frame");
-    Frame& f = c->frame;
-    if (!f.set || c->n_rows != c->height) return fail(c, CPT_ERR_STATE, "cpt_filter_frame: needs a full frame");
-    for (int y = 0; y < c->height; ++y)
-        if (c->rows_h[y] != y) return fail(c, CPT_ERR_STATE, "cpt_filter_frame: needs rows 0..height-1 in order");
-    const size_t npix = c->npix();
-    if (!f.adaptive.has_result(npix))
-        return fail(c, CPT_ERR_STATE, "cpt_filter_frame: no moments (cpt_render_adaptive or cpt_write_moments first)");
-    if (f.d_normal.capacity() < 3 * npix)
-        return fail(c, CPT_ERR_STATE, "cpt_filter_frame: no normals (render with CPT_RENDER_AUX or cpt_write_aux first)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = f.filter.d_plane[0].ensure(c, npix)) != CPT_OK || (rc = f.filter.d_plane[1].ensure(c, npix)) != CPT_OK ||
-        (rc = f.filter.d_ok.ensure(c, npix)) != CPT_OK)
-        return rc;
-    f.filter.result = -1;
-    hipStream_t s = c->stream();
-    HIP_TRY(c, hipEventRecord(c->t_filter.t0, s));
-    HIP_TRY(c, cpt::launch_filter_prepare(f.d_accum, f.adaptive.d_stat, npix, f.filter.d_plane[0], f.filter.d_ok, s));
-    for (int l = 0; l < levels; ++l)
-        HIP_TRY(c, cpt::launch_filter_level(f.filter.d_plane[l & 1], f.d_normal, f.filter.d_ok, f.filter.d_plane[(l + 1) & 1], c->width, c->height,
-                                           1 << l, sigma_l * sigma_l, normal_sharpness_log2, s));
-    HIP_TRY(c, hipEventRecord(c->t_filter.t1, s));
-    c->t_filter.recorded = true;
-    f.filter.result = levels & 1;
-    return CPT_OK;
+    return filter_frame(c, "cpt_filter_frame", false, levels, sigma_l, normal_sharpness_log2);
 }
 
 int cpt_filter_frame_spatial(cpt_ctx* c, int levels, float sigma_l, int normal_sharpness_log2) {
-    if (!c) return CPT_ERR_INVALID_ARG;
-    if (levels < 0 || levels > flt::MAX_LEVELS || !args_ok(sigma_l, normal_sharpness_log2))
-        return fail(c, CPT_ERR_INVALID_ARG,
-                    "cpt_filter_frame_spatial: levels %d (0..8), sigma_l %g (finite, >= 0), normal_sharpness_log2 %d (0..10)", levels,
-                    (double)sigma_l, normal_sharpness_log2);
-    CPT_REFUSE_PENDING(c, "cpt_filter_frame_spatial");
-    Frame& f = c->frame;
-    if (!f.set || c->n_rows != c->height) return fail(c, CPT_ERR_STATE, "cpt_filter_frame_spatial: needs a full frame");
-    for (int y = 0; y < c->height; ++y)
-        if (c->rows_h[y] != y) return fail(c, CPT_ERR_STATE, "cpt_filter_frame_spatial: needs rows 0..height-1 in order");
-    const size_t npix = c->npix();
-    const GBufferState& g = f.gbuffer;
-    if (!g.valid || g.d_id.capacity() < npix || g.d_normal.capacity() < 3 * npix)
-        return fail(c, CPT_ERR_STATE, "cpt_filter_frame_spatial: no G-buffer (cpt_gbuffer, a reprojection or cpt_write_gbuffer first)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = f.filter.d_plane[0].ensure(c, npix)) != CPT_OK || (rc = f.filter.d_plane[1].ensure(c, npix)) != CPT_OK ||
-        (rc = f.filter.d_ok.ensure(c, npix)) != CPT_OK)
-        return rc;
-    f.filter.result = -1;
-    hipStream_t s = c->stream();
-    HIP_TRY(c, hipEventRecord(c->t_filter.t0, s));
-    HIP_TRY(c, cpt::launch_filter_prepare_spatial(f.d_accum, g.d_id, g.d_normal, c->width, c->height, normal_sharpness_log2,
-                                                  f.filter.d_plane[0], f.filter.d_ok, s));
-    for (int l = 0; l < levels; ++l)
-        HIP_TRY(c, cpt::launch_filter_level_id(f.filter.d_plane[l & 1], g.d_normal, g.d_id, f.filter.d_ok, f.filter.d_plane[(l + 1) & 1],
-                                              c->width, c->height, 1 << l, sigma_l * sigma_l, normal_sharpness_log2, s));
-    HIP_TRY(c, hipEventRecord(c->t_filter.t1, s));
-    c->t_filter.recorded = true;
-    f.filter.result = levels & 1;
-    return CPT_OK;
+    return filter_frame(c, "cpt_filter_frame_spatial", true, levels, sigma_l, normal_sharpness_log2);
 }
 
 int cpt_read_filtered(cpt_ctx* c, float* rgb, float* variance, size_t capacity_pixels) {
@@ -112,12 +102,7 @@ int cpt_read_filtered(cpt_ctx* c, float* rgb, float* variance, size_t capacity_p
 }
 
 int cpt_last_filter_ms(cpt_ctx* c, float* ms) {
-    if (!c || !ms) return CPT_ERR_INVALID_ARG;
-    if (!c->t_filter.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_filter_ms: no cpt_filter_frame yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->t_filter.t1));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->t_filter.t0, c->t_filter.t1));
-    return CPT_OK;
+    return last_span_ms(c, &cpt_ctx::t_filter, ms, "cpt_last_filter_ms: no cpt_filter_frame yet");
 }
 
 int cpt_read_moments(cpt_ctx* c, float* planar4, size_t capacity) {

@@ -180,12 +180,7 @@ int cpt_pick(cpt_ctx* c, const cpt_camera* cam, int x, int y, uint32_t flags, in
 }
 
 int cpt_last_query_ms(cpt_ctx* c, float* ms) {
-    if (!c || !ms) return CPT_ERR_INVALID_ARG;
-    if (!c->t_query.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_query_ms: no query yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->t_query.t1));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->t_query.t0, c->t_query.t1));
-    return CPT_OK;
+    return last_span_ms(c, &cpt_ctx::t_query, ms, "cpt_last_query_ms: no query yet");
 }
 
 }  // extern "C"

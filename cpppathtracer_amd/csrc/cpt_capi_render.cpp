@@ -297,11 +297,7 @@ int cpt_launch_grid_host(int cus, int blocks_per_cu, int block, int64_t tiles, i
 }
 
 int cpt_last_render_ms(cpt_ctx* c, float* ms) {
-    if (!c || !ms) return CPT_ERR_INVALID_ARG;
-    if (!c->t_render.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_render_ms: nothing rendered");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->t_render.t1));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->t_render.t0, c->t_render.t1));
+    if (int rc = last_span_ms(c, &cpt_ctx::t_render, ms, "cpt_last_render_ms: nothing rendered")) return rc;
     c->last_kernel_ms = *ms;
     return CPT_OK;
 }

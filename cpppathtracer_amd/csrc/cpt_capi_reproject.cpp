@@ -2,13 +2,14 @@
 // cpt_reproject_accum) and of the display state (§22: cpt_reproject_display) to a
 // moved camera, the tracked variants that keep the history's G-buffer and follow object edits
 // (§23: cpt_history_capture, cpt_reproject_accum_tracked, cpt_reproject_display_tracked), their
-// timing, and the host-only entries on the same arithmetic.  The G-buffers
-// are cpt_query.hip's kernel, the look-ups cpt_reproject.hip's; the arithmetic is
-// cpt_reproject.hpp's on both sides.
+// timing, and the host-only entries on the same arithmetic.  The four device calls are one function,
+// `reproject`, the four host entries one, `reproject_host`.  The G-buffers are cpt_query.hip's
+// kernel, the look-up cpt_reproject.hip's; the arithmetic is cpt_reproject.hpp's on both sides.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <utility>
 
 #include "cpt_context.hpp"
@@ -24,7 +25,7 @@ constexpr uint32_t WALK_FLAGS = CPT_TRAVERSAL_ORDERED | CPT_TRAVERSAL_PLAIN_LEAV
 
 bool args_ok(int max_history, float plane_tol) { return max_history >= 1 && rp::finite(plane_tol) && plane_tol >= 0.f; }
 
-// What cpt_reproject_accum and cpt_reproject_display (`who`) ask before they write anything.
+// What every device call here (`who`) asks before it writes anything.
 int checked(cpt_ctx* c, const char* who, const cpt_camera* from, const cpt_camera* to, int max_history, float plane_tol,
             uint32_t flags) {
     if (!from || !to) return fail(c, CPT_ERR_INVALID_ARG, "%s: a camera is NULL", who);
@@ -33,9 +34,7 @@ int checked(cpt_ctx* c, const char* who, const cpt_camera* from, const cpt_camer
         return fail(c, CPT_ERR_INVALID_ARG, "%s: max_history %d (>= 1), plane_tol %g (finite, >= 0)", who, max_history,
                     (double)plane_tol);
     if (!c->scene_set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_scene first", who);
-    if (!c->frame.set || c->n_rows != c->height) return fail(c, CPT_ERR_STATE, "%s: needs a full frame", who);
-    for (int y = 0; y < c->height; ++y)
-        if (c->rows_h[y] != y) return fail(c, CPT_ERR_STATE, "%s: needs rows 0..height-1 in order", who);
+    if (int rc = require_full_frame(c, who)) return rc;
     CPT_REFUSE_PENDING(c, who);
     for (const cpt_camera* cam : {from, to})
         if (cam->width != c->width || cam->height != c->height)
@@ -45,7 +44,7 @@ int checked(cpt_ctx* c, const char* who, const cpt_camera* from, const cpt_camer
     return CPT_OK;
 }
 
-// The planes both calls trace into: the frame's G-buffer and the history's id and distance.
+// The planes every call traces into: the frame's G-buffer and the history's id and distance.
 int ensure_planes(cpt_ctx* c) {
     GBufferState& g = c->frame.gbuffer;
     ReprojectState& r = c->frame.reproject;
@@ -58,34 +57,30 @@ int ensure_planes(cpt_ctx* c) {
     return CPT_OK;
 }
 
-// The two traces, with the call's first three timing events: the G-buffer at `from` into the
-// history planes (its normals pass through the frame's normal plane, which the second trace
-// overwrites), then the G-buffer at `to` into the frame's own.
-int trace_pair(cpt_ctx* c, const cpt::KParams& p0, const cpt::KParams& p1, hipStream_t s) {
+// The whole G-buffer at p's camera into the frame's own planes (the kernel writes all four).
+int trace_gbuffer(cpt_ctx* c, const cpt::KParams& p, hipStream_t s) {
     GBufferState& g = c->frame.gbuffer;
-    ReprojectState& r = c->frame.reproject;
-    // the trace at `from` overwrites the planes a captured history lives in: it is gone
-    r.captured = false;
-    HIP_TRY(c, hipEventRecord(c->t_reproject.t0, s));
-    HIP_TRY(c, cpt::launch_ray_query(p0, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
-                                     cpt::QueryOut{r.d_id, r.d_t, g.d_normal, nullptr}, s));
-    HIP_TRY(c, hipEventRecord(c->ev_reproject[0], s));
-    HIP_TRY(c, cpt::launch_ray_query(p1, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
+    HIP_TRY(c, cpt::launch_ray_query(p, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
                                      cpt::QueryOut{g.d_id, g.d_t, g.d_normal, g.d_albedo}, s));
     g.valid = true;
-    HIP_TRY(c, hipEventRecord(c->ev_reproject[1], s));
     return CPT_OK;
 }
 
-// The tracked calls' one trace, with the same timing events: none at the captured camera (ms3[0]
-// reads 0), then the G-buffer at `to` into the frame's own.
-int trace_to(cpt_ctx* c, const cpt::KParams& p1, hipStream_t s) {
+// The traces, with the call's first three timing events: the G-buffer at `from` (p0) into the
+// history planes (its normals pass through the frame's normal plane, which the second trace
+// overwrites), then the G-buffer at `to` (p1) into the frame's own.  p0 == nullptr, the tracked
+// calls: no trace at the captured camera (ms3[0] reads 0).
+int trace(cpt_ctx* c, const cpt::KParams* p0, const cpt::KParams& p1, hipStream_t s) {
     GBufferState& g = c->frame.gbuffer;
+    ReprojectState& r = c->frame.reproject;
+    // the trace at `from` overwrites the planes a captured history lives in: it is gone
+    if (p0) r.captured = false;
     HIP_TRY(c, hipEventRecord(c->t_reproject.t0, s));
+    if (p0)
+        HIP_TRY(c, cpt::launch_ray_query(*p0, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
+                                         cpt::QueryOut{r.d_id, r.d_t, g.d_normal, nullptr}, s));
     HIP_TRY(c, hipEventRecord(c->ev_reproject[0], s));
-    HIP_TRY(c, cpt::launch_ray_query(p1, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
-                                     cpt::QueryOut{g.d_id, g.d_t, g.d_normal, g.d_albedo}, s));
-    g.valid = true;
+    if (int rc = trace_gbuffer(c, p1, s)) return rc;
     HIP_TRY(c, hipEventRecord(c->ev_reproject[1], s));
     return CPT_OK;
 }
@@ -142,105 +137,162 @@ void renew_history(cpt_ctx* c, const cpt_camera* to, bool edited) {
     if (edited) r.objs = c->objs;   // same size: assigns in place
 }
 
+// The four device calls.  Look: the accumulator's argument struct or the display's; TRACKED: `from`
+// is the captured history's camera (the caller gives none) and no trace runs there.
+template <typename Look, bool TRACKED>
+int reproject(cpt_ctx* c, const char* who, const cpt_camera* from, const cpt_camera* to, int max_history, float plane_tol,
+              uint32_t flags) {
+    constexpr bool DISPLAY = std::is_same_v<Look, cpt::ReprojectDisplayArgs>;
+    if (!c) return CPT_ERR_INVALID_ARG;
+    if (int rc = checked(c, who, TRACKED ? to : from, to, max_history, plane_tol, flags)) return rc;
+    Frame& f = c->frame;
+    DisplayBand& d = f.display;
+    GBufferState& g = f.gbuffer;
+    ReprojectState& r = f.reproject;
+    const int w_eff = 16 * (c->width / 16), h_eff = 16 * (c->height / 16);
+    if (DISPLAY) {
+        if (!d.d_mix) return fail(c, CPT_ERR_STATE, "%s: no display pass yet", who);
+        if (d.y0 != 0 || d.y1 != h_eff)
+            return fail(c, CPT_ERR_STATE, "%s: the display holds the band [%d, %d), not the full frame", who, d.y0, d.y1);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npix = c->npix();
+    int rc;
+    if ((rc = TRACKED ? tracked_ready(c, who) : ensure_planes(c)) != CPT_OK) return rc;
+    if (DISPLAY) {
+        if ((rc = d.d_mix_next.ensure(c, 3 * npix)) != CPT_OK || (rc = d.d_count_next.ensure(c, npix)) != CPT_OK) return rc;
+    } else if ((rc = r.d_accum.ensure(c, npix)) != CPT_OK) {
+        return rc;
+    }
+    if (TRACKED) from = &r.cam;
+    cpt::KParams p0, p1;
+    fill_params(c, from, 0, 0, flags, p0);
+    fill_params(c, to, 0, 0, flags, p1);
+    std::conditional_t<TRACKED, cpt::ReprojectTracked<Look>, Look> args;
+    std::memset(&args, 0, sizeof(args));
+    Look& a = cpt::look_of(args);
+    a.cam0 = p0.cam;
+    a.cam1 = p1.cam;
+    a.view0 = rp::old_view(*from);
+    a.width = c->width;
+    a.height = c->height;
+    a.id0 = r.d_id;
+    a.t0 = r.d_t;
+    a.id1 = g.d_id;
+    a.t1 = g.d_t;
+    a.normal1 = g.d_normal;
+    a.max_history = (float)max_history;
+    a.plane_tol = plane_tol;
+    if constexpr (DISPLAY) {
+        a.w_eff = w_eff;
+        a.h_eff = h_eff;
+        a.mean_in = d.d_mix;
+        a.count_in = d.d_count;
+        a.mean_out = d.d_mix_next;
+        a.count_out = d.d_count_next;
+    } else {
+        a.in = f.d_accum;
+        a.out = r.d_accum;
+    }
+    hipStream_t s = c->stream();
+    if (DISPLAY && (rc = d.fill_count(c)) != CPT_OK) return rc;
+    bool edited = false;
+    if constexpr (TRACKED) {
+        args.id_next = r.d_id_next;
+        args.t_next = r.d_t_next;
+        if ((rc = motion_table(c, s, &args.motion)) != CPT_OK) return rc;
+        edited = args.motion != nullptr;
+    }
+    if ((rc = trace(c, TRACKED ? nullptr : &p0, p1, s)) != CPT_OK) return rc;
+    HIP_TRY(c, cpt::launch_reproject(args, s));
+    HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
+    c->t_reproject.recorded = true;
+    c->reproject_tracked = TRACKED;
+    // the second planes are the accumulator, or the display state, from here on: work already queued
+    // holds the old pointers by value and runs before the kernel; every later call reads the members.
+    // The display's need no clearing: the kernel wrote every pixel of the frame.
+    if (DISPLAY) {
+        std::swap(d.d_mix, d.d_mix_next);
+        std::swap(d.d_count, d.d_count_next);
+    } else {
+        std::swap(f.d_accum, r.d_accum);
+        f.adaptive.done = false;   // the moments no longer describe the accumulator
+    }
+    if (TRACKED) renew_history(c, to, edited);
+    return CPT_OK;
+}
+
+// the tracked host entries' table: NULL with 0 records, or every hit's id inside it
+bool table_ok(const cpt_object_motion* table, int n_objs, const int32_t* id1, size_t npix) {
+    if (!table) return n_objs == 0;
+    if (n_objs <= 0) return false;
+    for (size_t i = 0; i < npix; ++i)
+        if (id1[i] >= n_objs) return false;
+    return true;
+}
+
+// The four host entries.  The accumulator's (`in`, `out`: [npix][4]; no count planes) or, DISPLAY,
+// the display state's (`in`, `out`: the mean [npix][3]); Motion: rp::NoMotion, or rp::TableMotion
+// with the `n_objs` records of its table.
+template <bool DISPLAY, typename Motion>
+int reproject_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0, const float* dir1,
+                   const int32_t* id0, const float* t0, const int32_t* id1, const float* t1, const float* normal1,
+                   const float* in, const float* count_in, const Motion& motion, int n_objs, int max_history, float plane_tol,
+                   float* out, float* count_out) {
+    if (!cam0 || !cam1 || width <= 0 || height <= 0 || !dir0 || !dir1 || !id0 || !t0 || !id1 || !t1 || !normal1 || !in || !out ||
+        in == out || (DISPLAY && (!count_in || !count_out || count_in == count_out)) || !args_ok(max_history, plane_tol))
+        return CPT_ERR_INVALID_ARG;
+    for (const cpt_camera* cam : {cam0, cam1})
+        if (cam->width != width || cam->height != height) return CPT_ERR_INVALID_ARG;
+    if constexpr (Motion::TRACKED)
+        if (!table_ok(motion.table, n_objs, id1, (size_t)width * height)) return CPT_ERR_INVALID_ARG;
+    const rp::OldView v = rp::old_view(*cam0);
+    const rp::V3 o1 = rp::v3_of(cam1->origin);
+    const auto src = [&] {
+        if constexpr (DISPLAY) return rp::DisplayPlaneSrc{in, count_in, id0, t0, dir0};
+        else return rp::PlaneSrc{reinterpret_cast<const rp::Px*>(in), id0, t0, dir0};
+    }();
+    const int w_eff = 16 * (width / 16), h_eff = 16 * (height / 16);
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const size_t i = (size_t)y * width + x;
+            const rp::V3 n1{normal1[3 * i], normal1[3 * i + 1], normal1[3 * i + 2]}, d1{dir1[3 * i], dir1[3 * i + 1], dir1[3 * i + 2]};
+            if constexpr (DISPLAY) {
+                const rp::Px r = rp::display_pixel(src, v, o1, width, height, w_eff, h_eff, x, y, id1[i], t1[i], n1, d1,
+                                                   (float)max_history, plane_tol, motion);
+                out[3 * i] = r.r;
+                out[3 * i + 1] = r.g;
+                out[3 * i + 2] = r.b;
+                count_out[i] = r.n;
+            } else {
+                reinterpret_cast<rp::Px*>(out)[i] =
+                    rp::pixel<false>(src, v, o1, width, height, id1[i], t1[i], n1, d1, (float)max_history, plane_tol, 0, 0, motion);
+            }
+        }
+    return CPT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int cpt_reproject_accum(cpt_ctx* c, const cpt_camera* from, const cpt_camera* to, int max_history, float plane_tol,
                         uint32_t flags) {
-    if (!c) return CPT_ERR_INVALID_ARG;
-    if (int rc = checked(c, "cpt_reproject_accum", from, to, max_history, plane_tol, flags)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    Frame& f = c->frame;
-    GBufferState& g = f.gbuffer;
-    ReprojectState& r = f.reproject;
-    int rc;
-    if ((rc = ensure_planes(c)) != CPT_OK || (rc = r.d_accum.ensure(c, c->npix())) != CPT_OK) return rc;
-    cpt::KParams p0, p1;
-    fill_params(c, from, 0, 0, flags, p0);
-    fill_params(c, to, 0, 0, flags, p1);
-    cpt::ReprojectArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cam0 = p0.cam;
-    a.cam1 = p1.cam;
-    a.view0 = rp::old_view(*from);
-    a.width = c->width;
-    a.height = c->height;
-    a.id0 = r.d_id;
-    a.t0 = r.d_t;
-    a.id1 = g.d_id;
-    a.t1 = g.d_t;
-    a.normal1 = g.d_normal;
-    a.in = f.d_accum;
-    a.out = r.d_accum;
-    a.max_history = (float)max_history;
-    a.plane_tol = plane_tol;
-    hipStream_t s = c->stream();
-    if ((rc = trace_pair(c, p0, p1, s)) != CPT_OK) return rc;
-    HIP_TRY(c, cpt::launch_reproject(a, s));
-    HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
-    c->t_reproject.recorded = true;
-    c->reproject_tracked = false;
-    // the second plane is the accumulator from here on: work already queued holds the old pointer
-    // by value and runs before the kernel; every later call reads the member
-    std::swap(f.d_accum, r.d_accum);
-    // the moments no longer describe the accumulator
-    f.adaptive.done = false;
-    return CPT_OK;
+    return reproject<cpt::ReprojectArgs, false>(c, "cpt_reproject_accum", from, to, max_history, plane_tol, flags);
 }
 
 int cpt_reproject_display(cpt_ctx* c, const cpt_camera* from, const cpt_camera* to, int max_history, float plane_tol,
                           uint32_t flags) {
-    if (!c) return CPT_ERR_INVALID_ARG;
-    if (int rc = checked(c, "cpt_reproject_display", from, to, max_history, plane_tol, flags)) return rc;
-    Frame& f = c->frame;
-    DisplayBand& d = f.display;
-    const int w_eff = 16 * (c->width / 16), h_eff = 16 * (c->height / 16);
-    if (!d.d_mix) return fail(c, CPT_ERR_STATE, "cpt_reproject_display: no display pass yet");
-    if (d.y0 != 0 || d.y1 != h_eff)
-        return fail(c, CPT_ERR_STATE, "cpt_reproject_display: the display holds the band [%d, %d), not the full frame", d.y0, d.y1);
-    HIP_TRY(c, hipSetDevice(c->device));
-    GBufferState& g = f.gbuffer;
-    ReprojectState& r = f.reproject;
-    const size_t npix = c->npix();
-    int rc;
-    if ((rc = ensure_planes(c)) != CPT_OK || (rc = d.d_mix_next.ensure(c, 3 * npix)) != CPT_OK ||
-        (rc = d.d_count_next.ensure(c, npix)) != CPT_OK)
-        return rc;
-    cpt::KParams p0, p1;
-    fill_params(c, from, 0, 0, flags, p0);
-    fill_params(c, to, 0, 0, flags, p1);
-    cpt::ReprojectDisplayArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.cam0 = p0.cam;
-    a.cam1 = p1.cam;
-    a.view0 = rp::old_view(*from);
-    a.width = c->width;
-    a.height = c->height;
-    a.w_eff = w_eff;
-    a.h_eff = h_eff;
-    a.id0 = r.d_id;
-    a.t0 = r.d_t;
-    a.id1 = g.d_id;
-    a.t1 = g.d_t;
-    a.normal1 = g.d_normal;
-    a.mean_in = d.d_mix;
-    a.count_in = d.d_count;
-    a.mean_out = d.d_mix_next;
-    a.count_out = d.d_count_next;
-    a.max_history = (float)max_history;
-    a.plane_tol = plane_tol;
-    hipStream_t s = c->stream();
-    if ((rc = d.fill_count(c)) != CPT_OK || (rc = trace_pair(c, p0, p1, s)) != CPT_OK) return rc;
-    HIP_TRY(c, cpt::launch_reproject_display(a, s));
-    HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
-    c->t_reproject.recorded = true;
-    c->reproject_tracked = false;
-    // the second planes are the display state from here on (as the accumulator's above); the
-    // kernel wrote every pixel of the frame, so they need no clearing
-    std::swap(d.d_mix, d.d_mix_next);
-    std::swap(d.d_count, d.d_count_next);
-    return CPT_OK;
+    return reproject<cpt::ReprojectDisplayArgs, false>(c, "cpt_reproject_display", from, to, max_history, plane_tol, flags);
+}
+
+int cpt_reproject_accum_tracked(cpt_ctx* c, const cpt_camera* to, int max_history, float plane_tol, uint32_t flags) {
+    return reproject<cpt::ReprojectArgs, true>(c, "cpt_reproject_accum_tracked", nullptr, to, max_history, plane_tol, flags);
+}
+
+int cpt_reproject_display_tracked(cpt_ctx* c, const cpt_camera* to, int max_history, float plane_tol, uint32_t flags) {
+    return reproject<cpt::ReprojectDisplayArgs, true>(c, "cpt_reproject_display_tracked", nullptr, to, max_history, plane_tol,
+                                                      flags);
 }
 
 int cpt_history_capture(cpt_ctx* c, const cpt_camera* cam, uint32_t flags) {
@@ -261,11 +313,8 @@ int cpt_history_capture(cpt_ctx* c, const cpt_camera* cam, uint32_t flags) {
     cpt::KParams p;
     fill_params(c, cam, 0, 0, flags, p);
     hipStream_t s = c->stream();
-    // the whole G-buffer at cam into the frame's own (the kernel writes all four planes), then its
-    // id and distance into the history's
-    HIP_TRY(c, cpt::launch_ray_query(p, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
-                                     cpt::QueryOut{g.d_id, g.d_t, g.d_normal, g.d_albedo}, s));
-    g.valid = true;
+    // the G-buffer at cam, then its id and distance into the history's planes
+    if (int rc = trace_gbuffer(c, p, s)) return rc;
     HIP_TRY(c, hipMemcpyAsync(r.d_id, g.d_id, c->npix() * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(r.d_t, g.d_t, c->npix() * sizeof(float), hipMemcpyDeviceToDevice, s));
     r.cam = *cam;
@@ -281,122 +330,17 @@ int cpt_history_info(cpt_ctx* c, int* valid, cpt_camera* cam) {
     return CPT_OK;
 }
 
-int cpt_reproject_accum_tracked(cpt_ctx* c, const cpt_camera* to, int max_history, float plane_tol, uint32_t flags) {
-    if (!c) return CPT_ERR_INVALID_ARG;
-    const char* who = "cpt_reproject_accum_tracked";
-    if (int rc = checked(c, who, to, to, max_history, plane_tol, flags)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    Frame& f = c->frame;
-    GBufferState& g = f.gbuffer;
-    ReprojectState& r = f.reproject;
-    int rc;
-    if ((rc = tracked_ready(c, who)) != CPT_OK || (rc = r.d_accum.ensure(c, c->npix())) != CPT_OK) return rc;
-    cpt::KParams p0, p1;
-    fill_params(c, &r.cam, 0, 0, flags, p0);
-    fill_params(c, to, 0, 0, flags, p1);
-    cpt::ReprojectTrackedArgs ta;
-    std::memset(&ta, 0, sizeof(ta));
-    cpt::ReprojectArgs& a = ta.look;
-    a.cam0 = p0.cam;
-    a.cam1 = p1.cam;
-    a.view0 = rp::old_view(r.cam);
-    a.width = c->width;
-    a.height = c->height;
-    a.id0 = r.d_id;
-    a.t0 = r.d_t;
-    a.id1 = g.d_id;
-    a.t1 = g.d_t;
-    a.normal1 = g.d_normal;
-    a.in = f.d_accum;
-    a.out = r.d_accum;
-    a.max_history = (float)max_history;
-    a.plane_tol = plane_tol;
-    ta.id_next = r.d_id_next;
-    ta.t_next = r.d_t_next;
-    hipStream_t s = c->stream();
-    if ((rc = motion_table(c, s, &ta.motion)) != CPT_OK || (rc = trace_to(c, p1, s)) != CPT_OK) return rc;
-    HIP_TRY(c, cpt::launch_reproject_tracked(ta, s));
-    HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
-    c->t_reproject.recorded = true;
-    c->reproject_tracked = true;
-    std::swap(f.d_accum, r.d_accum);   // as cpt_reproject_accum
-    f.adaptive.done = false;
-    renew_history(c, to, ta.motion != nullptr);
-    return CPT_OK;
-}
-
-int cpt_reproject_display_tracked(cpt_ctx* c, const cpt_camera* to, int max_history, float plane_tol, uint32_t flags) {
-    if (!c) return CPT_ERR_INVALID_ARG;
-    const char* who = "cpt_reproject_display_tracked";
-    if (int rc = checked(c, who, to, to, max_history, plane_tol, flags)) return rc;
-    Frame& f = c->frame;
-    DisplayBand& d = f.display;
-    const int w_eff = 16 * (c->width / 16), h_eff = 16 * (c->height / 16);
-    if (!d.d_mix) return fail(c, CPT_ERR_STATE, "%s: no display pass yet", who);
-    if (d.y0 != 0 || d.y1 != h_eff)
-        return fail(c, CPT_ERR_STATE, "%s: the display holds the band [%d, %d), not the full frame", who, d.y0, d.y1);
-    HIP_TRY(c, hipSetDevice(c->device));
-    GBufferState& g = f.gbuffer;
-    ReprojectState& r = f.reproject;
-    const size_t npix = c->npix();
-    int rc;
-    if ((rc = tracked_ready(c, who)) != CPT_OK || (rc = d.d_mix_next.ensure(c, 3 * npix)) != CPT_OK ||
-        (rc = d.d_count_next.ensure(c, npix)) != CPT_OK)
-        return rc;
-    cpt::KParams p0, p1;
-    fill_params(c, &r.cam, 0, 0, flags, p0);
-    fill_params(c, to, 0, 0, flags, p1);
-    cpt::ReprojectDisplayTrackedArgs ta;
-    std::memset(&ta, 0, sizeof(ta));
-    cpt::ReprojectDisplayArgs& a = ta.look;
-    a.cam0 = p0.cam;
-    a.cam1 = p1.cam;
-    a.view0 = rp::old_view(r.cam);
-    a.width = c->width;
-    a.height = c->height;
-    a.w_eff = w_eff;
-    a.h_eff = h_eff;
-    a.id0 = r.d_id;
-    a.t0 = r.d_t;
-    a.id1 = g.d_id;
-    a.t1 = g.d_t;
-    a.normal1 = g.d_normal;
-    a.mean_in = d.d_mix;
-    a.count_in = d.d_count;
-    a.mean_out = d.d_mix_next;
-    a.count_out = d.d_count_next;
-    a.max_history = (float)max_history;
-    a.plane_tol = plane_tol;
-    ta.id_next = r.d_id_next;
-    ta.t_next = r.d_t_next;
-    hipStream_t s = c->stream();
-    if ((rc = d.fill_count(c)) != CPT_OK || (rc = motion_table(c, s, &ta.motion)) != CPT_OK ||
-        (rc = trace_to(c, p1, s)) != CPT_OK)
-        return rc;
-    HIP_TRY(c, cpt::launch_reproject_display_tracked(ta, s));
-    HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
-    c->t_reproject.recorded = true;
-    c->reproject_tracked = true;
-    std::swap(d.d_mix, d.d_mix_next);   // as cpt_reproject_display
-    std::swap(d.d_count, d.d_count_next);
-    renew_history(c, to, ta.motion != nullptr);
-    return CPT_OK;
-}
-
 int cpt_last_reproject_ms(cpt_ctx* c, float* ms) {
-    if (!c || !ms) return CPT_ERR_INVALID_ARG;
-    if (!c->t_reproject.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_reproject_ms: no reprojection call (cpt_reproject_accum, _display or their tracked variants) yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->t_reproject.t1));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->t_reproject.t0, c->t_reproject.t1));
-    return CPT_OK;
+    return last_span_ms(c, &cpt_ctx::t_reproject, ms,
+                        "cpt_last_reproject_ms: no reprojection call (cpt_reproject_accum, _display or their tracked variants) yet");
 }
 
 int cpt_last_reproject_launch_ms(cpt_ctx* c, float* ms3) {
-    if (!c || !ms3) return CPT_ERR_INVALID_ARG;
-    if (!c->t_reproject.recorded) return fail(c, CPT_ERR_STATE, "cpt_last_reproject_launch_ms: no reprojection call (cpt_reproject_accum, _display or their tracked variants) yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->t_reproject.t1));
+    if (!ms3) return CPT_ERR_INVALID_ARG;
+    float all;   // read for its checks and its wait for t1
+    if (int rc = last_span_ms(c, &cpt_ctx::t_reproject, &all,
+                              "cpt_last_reproject_launch_ms: no reprojection call (cpt_reproject_accum, _display or their tracked variants) yet"))
+        return rc;
     const hipEvent_t ev[4] = {c->t_reproject.t0, c->ev_reproject[0], c->ev_reproject[1], c->t_reproject.t1};
     for (int k = 0; k < 3; ++k) HIP_TRY(c, hipEventElapsedTime(ms3 + k, ev[k], ev[k + 1]));
     if (c->reproject_tracked) ms3[0] = 0.f;   // no trace ran between the first two events
@@ -406,47 +350,16 @@ int cpt_last_reproject_launch_ms(cpt_ctx* c, float* ms3) {
 int cpt_reproject_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0,
                        const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
                        const float* normal1, const float* accum_in, int max_history, float plane_tol, float* accum_out) {
-    if (!cam0 || !cam1 || width <= 0 || height <= 0 || !dir0 || !dir1 || !id0 || !t0 || !id1 || !t1 || !normal1 || !accum_in ||
-        !accum_out || accum_in == accum_out || !args_ok(max_history, plane_tol))
-        return CPT_ERR_INVALID_ARG;
-    for (const cpt_camera* cam : {cam0, cam1})
-        if (cam->width != width || cam->height != height) return CPT_ERR_INVALID_ARG;
-    const rp::OldView v = rp::old_view(*cam0);
-    const rp::V3 o1 = rp::v3_of(cam1->origin);
-    const rp::PlaneSrc src{reinterpret_cast<const rp::Px*>(accum_in), id0, t0, dir0};
-    rp::Px* out = reinterpret_cast<rp::Px*>(accum_out);
-    const size_t npix = (size_t)width * height;
-    for (size_t i = 0; i < npix; ++i)
-        out[i] = rp::pixel(src, v, o1, width, height, id1[i], t1[i], rp::V3{normal1[3 * i], normal1[3 * i + 1], normal1[3 * i + 2]},
-                           rp::V3{dir1[3 * i], dir1[3 * i + 1], dir1[3 * i + 2]}, (float)max_history, plane_tol);
-    return CPT_OK;
+    return reproject_host<false>(cam0, cam1, width, height, dir0, dir1, id0, t0, id1, t1, normal1, accum_in, nullptr, rp::NoMotion{},
+                                 0, max_history, plane_tol, accum_out, nullptr);
 }
 
 int cpt_reproject_display_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0,
                                const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
                                const float* normal1, const float* mean_in, const float* count_in, int max_history,
                                float plane_tol, float* mean_out, float* count_out) {
-    if (!cam0 || !cam1 || width <= 0 || height <= 0 || !dir0 || !dir1 || !id0 || !t0 || !id1 || !t1 || !normal1 || !mean_in ||
-        !count_in || !mean_out || !count_out || mean_in == mean_out || count_in == count_out || !args_ok(max_history, plane_tol))
-        return CPT_ERR_INVALID_ARG;
-    for (const cpt_camera* cam : {cam0, cam1})
-        if (cam->width != width || cam->height != height) return CPT_ERR_INVALID_ARG;
-    const rp::OldView v = rp::old_view(*cam0);
-    const rp::V3 o1 = rp::v3_of(cam1->origin);
-    const rp::DisplayPlaneSrc src{mean_in, count_in, id0, t0, dir0};
-    const int w_eff = 16 * (width / 16), h_eff = 16 * (height / 16);
-    for (int y = 0; y < height; ++y)
-        for (int x = 0; x < width; ++x) {
-            const size_t i = (size_t)y * width + x;
-            const rp::Px r = rp::display_pixel(src, v, o1, width, height, w_eff, h_eff, x, y, id1[i], t1[i],
-                                               rp::V3{normal1[3 * i], normal1[3 * i + 1], normal1[3 * i + 2]},
-                                               rp::V3{dir1[3 * i], dir1[3 * i + 1], dir1[3 * i + 2]}, (float)max_history, plane_tol);
-            mean_out[3 * i] = r.r;
-            mean_out[3 * i + 1] = r.g;
-            mean_out[3 * i + 2] = r.b;
-            count_out[i] = r.n;
-        }
-    return CPT_OK;
+    return reproject_host<true>(cam0, cam1, width, height, dir0, dir1, id0, t0, id1, t1, normal1, mean_in, count_in, rp::NoMotion{},
+                                0, max_history, plane_tol, mean_out, count_out);
 }
 
 int cpt_object_motion_host(const cpt_object* old_objs, const cpt_object* new_objs, int n, cpt_object_motion* out_table) {
@@ -455,35 +368,12 @@ int cpt_object_motion_host(const cpt_object* old_objs, const cpt_object* new_obj
     return CPT_OK;
 }
 
-// the tracked host entries' table: NULL with 0 records, or every hit's id inside it
-static bool table_ok(const cpt_object_motion* table, int n_objs, const int32_t* id1, size_t npix) {
-    if (!table) return n_objs == 0;
-    if (n_objs <= 0) return false;
-    for (size_t i = 0; i < npix; ++i)
-        if (id1[i] >= n_objs) return false;
-    return true;
-}
-
 int cpt_reproject_tracked_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height, const float* dir0,
                                const float* dir1, const int32_t* id0, const float* t0, const int32_t* id1, const float* t1,
                                const float* normal1, const float* accum_in, const cpt_object_motion* table, int n_objs,
                                int max_history, float plane_tol, float* accum_out) {
-    if (!cam0 || !cam1 || width <= 0 || height <= 0 || !dir0 || !dir1 || !id0 || !t0 || !id1 || !t1 || !normal1 || !accum_in ||
-        !accum_out || accum_in == accum_out || !args_ok(max_history, plane_tol))
-        return CPT_ERR_INVALID_ARG;
-    for (const cpt_camera* cam : {cam0, cam1})
-        if (cam->width != width || cam->height != height) return CPT_ERR_INVALID_ARG;
-    const size_t npix = (size_t)width * height;
-    if (!table_ok(table, n_objs, id1, npix)) return CPT_ERR_INVALID_ARG;
-    const rp::OldView v = rp::old_view(*cam0);
-    const rp::V3 o1 = rp::v3_of(cam1->origin);
-    const rp::PlaneSrc src{reinterpret_cast<const rp::Px*>(accum_in), id0, t0, dir0};
-    rp::Px* out = reinterpret_cast<rp::Px*>(accum_out);
-    for (size_t i = 0; i < npix; ++i)
-        out[i] = rp::pixel<false, rp::PlaneSrc, rp::TableMotion>(
-            src, v, o1, width, height, id1[i], t1[i], rp::V3{normal1[3 * i], normal1[3 * i + 1], normal1[3 * i + 2]},
-            rp::V3{dir1[3 * i], dir1[3 * i + 1], dir1[3 * i + 2]}, (float)max_history, plane_tol, 0, 0, rp::TableMotion{table});
-    return CPT_OK;
+    return reproject_host<false>(cam0, cam1, width, height, dir0, dir1, id0, t0, id1, t1, normal1, accum_in, nullptr,
+                                 rp::TableMotion{table}, n_objs, max_history, plane_tol, accum_out, nullptr);
 }
 
 int cpt_reproject_display_tracked_host(const cpt_camera* cam0, const cpt_camera* cam1, int width, int height,
@@ -491,29 +381,8 @@ int cpt_reproject_display_tracked_host(const cpt_camera* cam0, const cpt_camera*
                                        const int32_t* id1, const float* t1, const float* normal1, const float* mean_in,
                                        const float* count_in, const cpt_object_motion* table, int n_objs, int max_history,
                                        float plane_tol, float* mean_out, float* count_out) {
-    if (!cam0 || !cam1 || width <= 0 || height <= 0 || !dir0 || !dir1 || !id0 || !t0 || !id1 || !t1 || !normal1 || !mean_in ||
-        !count_in || !mean_out || !count_out || mean_in == mean_out || count_in == count_out || !args_ok(max_history, plane_tol))
-        return CPT_ERR_INVALID_ARG;
-    for (const cpt_camera* cam : {cam0, cam1})
-        if (cam->width != width || cam->height != height) return CPT_ERR_INVALID_ARG;
-    if (!table_ok(table, n_objs, id1, (size_t)width * height)) return CPT_ERR_INVALID_ARG;
-    const rp::OldView v = rp::old_view(*cam0);
-    const rp::V3 o1 = rp::v3_of(cam1->origin);
-    const rp::DisplayPlaneSrc src{mean_in, count_in, id0, t0, dir0};
-    const int w_eff = 16 * (width / 16), h_eff = 16 * (height / 16);
-    for (int y = 0; y < height; ++y)
-        for (int x = 0; x < width; ++x) {
-            const size_t i = (size_t)y * width + x;
-            const rp::Px r = rp::display_pixel(src, v, o1, width, height, w_eff, h_eff, x, y, id1[i], t1[i],
-                                               rp::V3{normal1[3 * i], normal1[3 * i + 1], normal1[3 * i + 2]},
-                                               rp::V3{dir1[3 * i], dir1[3 * i + 1], dir1[3 * i + 2]}, (float)max_history, plane_tol,
-                                               rp::TableMotion{table});
-            mean_out[3 * i] = r.r;
-            mean_out[3 * i + 1] = r.g;
-            mean_out[3 * i + 2] = r.b;
-            count_out[i] = r.n;
-        }
-    return CPT_OK;
+    return reproject_host<true>(cam0, cam1, width, height, dir0, dir1, id0, t0, id1, t1, normal1, mean_in, count_in,
+                                rp::TableMotion{table}, n_objs, max_history, plane_tol, mean_out, count_out);
 }
 
 }  // extern "C"

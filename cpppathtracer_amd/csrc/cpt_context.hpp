@@ -333,6 +333,11 @@ inline int refuse_pending(cpt_ctx* c, const char* who) {
         if (int rc_ = refuse_pending((ctx), (who))) return rc_;  \
     } while (0)
 
+// CPT_ERR_STATE from `who` unless the frame holds every row, 0..height-1 in order (cpt_capi.cpp).
+int require_full_frame(cpt_ctx* c, const char* who);
+// The milliseconds between a span's two events, behind a cpt_last_*_ms entry: CPT_ERR_INVALID_ARG for
+// a NULL c or ms, CPT_ERR_STATE with `nothing_yet` while nothing was recorded; waits for t1 (cpt_capi.cpp).
+int last_span_ms(cpt_ctx* c, TimedSpan cpt_ctx::*span, float* ms, const char* nothing_yet);
 // Drain the context's stream, then report a device-side error of the work it ran.
 int check_device_error(cpt_ctx* c);
 int sync_checked(cpt_ctx* c);

@@ -308,10 +308,10 @@ struct DisplayPlaneSrc {
 
 }  // namespace reproject
 
-// k_reproject_accum's arguments (cpt_reproject.hip): both cameras as ray_gen_centre reads them, the
-// old one as the projection reads it, the G-buffer planes of a width x height full frame (id0, t0
-// at the old camera; id1, t1, normal1 at the new one), the accumulator and the plane the result
-// goes to (not the same).
+// The arguments of k_reproject (cpt_reproject.hip), one struct per look-up.  The accumulator's: both
+// cameras as ray_gen_centre reads them, the old one as the projection reads it, the G-buffer planes
+// of a width x height full frame (id0, t0 at the old camera; id1, t1, normal1 at the new one), the
+// accumulator and the plane the result goes to (not the same).
 struct ReprojectArgs {
     CamK cam0, cam1;
     reproject::OldView view0;
@@ -325,11 +325,10 @@ struct ReprojectArgs {
     float4* out;
     float max_history, plane_tol;
 };
-hipError_t launch_reproject(const ReprojectArgs& a, hipStream_t stream);
 
-// k_reproject_display's arguments: the same cameras and G-buffer planes; the display state of the
-// width x height frame (the Mix mean [npix][3] and the count plane [npix], of which the launch
-// region w_eff x h_eff is used) and the planes the result goes to (not the same).
+// The display's: the same cameras and G-buffer planes; the display state of the width x height
+// frame (the Mix mean [npix][3] and the count plane [npix], of which the launch region
+// w_eff x h_eff is used) and the planes the result goes to (not the same).
 struct ReprojectDisplayArgs {
     CamK cam0, cam1;
     reproject::OldView view0;
@@ -345,26 +344,28 @@ struct ReprojectDisplayArgs {
     float* count_out;
     float max_history, plane_tol;
 };
-hipError_t launch_reproject_display(const ReprojectDisplayArgs& a, hipStream_t stream);
 
-// k_reproject_accum_tracked's and k_reproject_display_tracked's arguments: the
-// untracked kernel's, with id0 / t0 the captured history's planes and cam0 / view0 its camera; the
-// motion table (one record per object index; nullptr: no object was edited since the capture) and
-// the planes that take the new frame's id and distance, the next call's history (not id0 / t0).
-struct ReprojectTrackedArgs {
-    ReprojectArgs look;
+// A tracked look-up's: the untracked one's, with id0 / t0 the captured history's
+// planes and cam0 / view0 its camera; the motion table (one record per object index; nullptr: no
+// object was edited since the capture) and the planes that take the new frame's id and distance,
+// the next call's history (not id0 / t0).
+template <typename Look>
+struct ReprojectTracked {
+    Look look;
     const cpt_object_motion* motion;
     int32_t* id_next;
     float* t_next;
 };
-hipError_t launch_reproject_tracked(const ReprojectTrackedArgs& a, hipStream_t stream);
 
-struct ReprojectDisplayTrackedArgs {
-    ReprojectDisplayArgs look;
-    const cpt_object_motion* motion;
-    int32_t* id_next;
-    float* t_next;
-};
-hipError_t launch_reproject_display_tracked(const ReprojectDisplayTrackedArgs& a, hipStream_t stream);
+template <typename Args> constexpr bool is_tracked = false;
+template <typename Look> constexpr bool is_tracked<ReprojectTracked<Look>> = true;
+
+// The untracked struct inside either kind of argument.
+template <typename Look> __host__ __device__ inline Look& look_of(ReprojectTracked<Look>& a) { return a.look; }
+template <typename Look> __host__ __device__ inline const Look& look_of(const ReprojectTracked<Look>& a) { return a.look; }
+template <typename Look> __host__ __device__ inline Look& look_of(Look& a) { return a; }
+
+// Defined in cpt_reproject.hip for the four argument types.
+template <typename Args> hipError_t launch_reproject(const Args& args, hipStream_t stream);
 
 }  // namespace cpt
