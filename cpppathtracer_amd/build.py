@@ -37,6 +37,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_scene.cpp"),
     os.path.join(CSRC, "cpt_host_bvh.cpp"),
     os.path.join(CSRC, "cpt_host_rng.cpp"),
+    os.path.join(CSRC, "cpt_api_scene.cpp"),
     os.path.join(CSRC, "cpt_api.cpp"),
 ]
 

@@ -1,280 +1,15 @@
-// cpt_api.cpp — the reference-shaped C++ construction API (include/cpppathtracer/*.h) on top
-// of the C-ABI (include/cpt.h).  Host code only; every GPU operation goes through cpt_*.
+// cpt_api.cpp — PathTracer of the reference-shaped C++ construction API
+// (include/cpppathtracer/path_tracer.h) on top of the C-ABI (include/cpt.h); the classes that never
+// see a context are in cpt_api_scene.cpp.  Host code only; every GPU operation goes through cpt_*.
 #include <dlfcn.h>
 
-#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <algorithm>
-#include <map>
 #include <mutex>
-#include <set>
-#include <sstream>
 
 #include "../../include/cpppathtracer/path_tracer.h"
-
-// ======================================================================================
-// Object (object.cu:134-170)
-// ======================================================================================
-float3 Object::GetAABBMax() {
-    float3 m = make_float3(0.f);
-    const float tol = BOUNCE_RAY_TMIN * 5.f;
-    switch (type_) {
-        case PrimitiveType::Sphere: m = center_ + make_float3(ABS(radius_)); break;
-        case PrimitiveType::Platform: m = make_float3(DEFAULT_RAY_TMAX * 5, y_pos_ + tol, DEFAULT_RAY_TMAX * 5); break;
-        case PrimitiveType::Cylinder:
-            m = make_float3(center_.x + ABS(radius_), center_.y + height_ / 2 + tol, center_.z + ABS(radius_));
-            break;
-        default: break;
-    }
-    return m;
-}
-
-float3 Object::GetAABBMin() {
-    float3 m = make_float3(0.f);
-    const float tol = BOUNCE_RAY_TMIN * 5.f;
-    switch (type_) {
-        case PrimitiveType::Sphere: m = center_ - make_float3(ABS(radius_)); break;
-        case PrimitiveType::Platform: m = make_float3(-DEFAULT_RAY_TMAX * 5, y_pos_ - tol, -DEFAULT_RAY_TMAX * 5); break;
-        case PrimitiveType::Cylinder:
-            m = make_float3(center_.x - ABS(radius_), center_.y - height_ / 2 - tol, center_.z - ABS(radius_));
-            break;
-        default: break;
-    }
-    return m;
-}
-
-// ======================================================================================
-// MotionalCamera (motional_camera.cu)
-// ======================================================================================
-static std::mutex camera_mutex;   // motional_camera.cu:12
-
-MotionalCamera::MotionalCamera()
-    : width_(1920), height_(1080), cur_sample_idx_(0), origin_(make_float3(0.f)), look_at_(make_float3(0.f, 0.f, 1.f)) {}
-MotionalCamera::MotionalCamera(int width, int height)
-    : width_(width), height_(height), cur_sample_idx_(0), origin_(make_float3(0.f)), look_at_(make_float3(0.f, 0.f, 1.f)) {}
-MotionalCamera::MotionalCamera(int width, int height, float3 ori, float3 at)
-    : width_(width), height_(height), cur_sample_idx_(0), origin_(ori), look_at_(at) {}
-MotionalCamera::~MotionalCamera() {}
-
-void MotionalCamera::Refresh() { cur_sample_idx_ = 0; }
-void MotionalCamera::SetViewFov(float fov) { view_fov_ = fov; }
-void MotionalCamera::Resize(int width, int height) { width_ = width; height_ = height; }
-void MotionalCamera::SetOrigin(float3 ori) { origin_ = ori; }
-void MotionalCamera::SetOrigin(float x, float y, float z) { origin_ = make_float3(x, y, z); }
-void MotionalCamera::SetLookAt(float3 look_at) { look_at_ = look_at; }
-void MotionalCamera::SetLookAt(float x, float y, float z) { look_at_ = make_float3(x, y, z); }
-
-// Interactive camera controls (motional_camera.cu:76-168).  SURVEY.md §2 puts them outside
-// the hot path; they are kept only so the public MotionalCamera API is complete.  This is an
-// API-behaviour restatement: a move is origin/look_at += (k * move_speed) * axis along the
-// eye's left / back / up axis (a negated axis for the opposite move, which rounds exactly as
-// the reference's -=), and a turn re-normalises look_at onto the unit sphere around the eye,
-// steps it along the eye's left or up axis and re-normalises, with the reference's float
-// operations in the reference's order.
-namespace {
-float3 eye_left(const MotionalCamera& c) { return -normalize(cross(c.vup, normalize(c.origin_ - c.look_at_))); }
-float3 eye_back(const MotionalCamera& c) { return -normalize(cross(eye_left(c), c.vup)); }
-
-void translate(MotionalCamera& c, float3 axis, float k) {
-    c.origin_ += k * c.move_speed_ * axis;
-    c.look_at_ += k * c.move_speed_ * axis;
-}
-
-// `up`: step along the up axis (else the left axis) by d.
-void turn(MotionalCamera& c, bool up, float d) {
-    c.look_at_ = c.origin_ + normalize(c.look_at_ - c.origin_);
-    const float3 w = normalize(c.look_at_ - c.origin_);
-    const float3 left = normalize(cross(c.vup, w));
-    const float3 axis = up ? normalize(cross(w, left)) : left;
-    c.look_at_ += d * axis;
-    c.look_at_ = c.origin_ + normalize(c.look_at_ - c.origin_);
-}
-}  // namespace
-
-void MotionalCamera::MoveEyeLeft(float k) { translate(*this, eye_left(*this), k); }
-void MotionalCamera::MoveEyeRight(float k) { translate(*this, -eye_left(*this), k); }
-void MotionalCamera::MoveEyeForward(float k) { translate(*this, -eye_back(*this), k); }
-void MotionalCamera::MoveEyeBackward(float k) { translate(*this, eye_back(*this), k); }
-void MotionalCamera::MoveEyeUp(float k) { translate(*this, vup, k); }
-void MotionalCamera::MoveEyeDown(float k) { translate(*this, -vup, k); }
-void MotionalCamera::RotateAroundUp(float dy) { turn(*this, true, dy); }
-void MotionalCamera::RotateAroundDown(float dy) { turn(*this, true, -dy); }
-void MotionalCamera::RotateAroundLeft(float dx) { turn(*this, false, dx); }
-void MotionalCamera::RotateAroundRight(float dx) { turn(*this, false, -dx); }
-void MotionalCamera::ScaleFov(float d) { view_fov_ = (float)(view_fov_ + d * M_PI / 180.0f); }
-void MotionalCamera::Lock() { camera_mutex.lock(); }
-void MotionalCamera::Unlock() { camera_mutex.unlock(); }
-
-MotionalCamera MotionalCamera::GetCopy() {
-    std::lock_guard<std::mutex> lock(camera_mutex);
-    cpt_camera_get_copy(reinterpret_cast<cpt_camera*>(this));   // basis + cur_sample_idx_++
-    return *this;
-}
-
-// ======================================================================================
-// SceneBVH statics (bvh.cu:16-29, 116-165)
-// ======================================================================================
-namespace {
-std::mutex bvh_mutex;
-std::vector<Object*> bvh_objs;
-std::set<Object*> bvh_seen;
-std::vector<cpt_object> bvh_built;      // BuildBVH's by-value copies (bvh.cu:43)
-std::vector<cpt_object> bvh_current;    // ... with UpdateObject's re-copies
-std::vector<uint64_t> bvh_updates;      // UpdateObject calls per object since the build
-uint64_t bvh_build_id = 0, bvh_revision = 0;
-SceneBVH* const bvh_handle = reinterpret_cast<SceneBVH*>(&bvh_built);   // opaque, non-null
-
-// texture registry
-std::mutex tex_mutex;
-std::map<PocaTexture, PocaTextureData> tex_registry;
-PocaTexture tex_next = 1;
-}  // namespace
-
-void SceneBVH::AddObject(Object* obj) {
-    std::lock_guard<std::mutex> lk(bvh_mutex);
-    if (obj == nullptr || bvh_seen.count(obj)) return;
-    bvh_objs.push_back(obj);
-    bvh_seen.insert(obj);
-}
-
-SceneBVHGPUHandle SceneBVH::BuildBVH() {
-    std::lock_guard<std::mutex> lk(bvh_mutex);
-    bvh_built.resize(bvh_objs.size());
-    for (size_t i = 0; i < bvh_objs.size(); ++i) std::memcpy(&bvh_built[i], bvh_objs[i], sizeof(cpt_object));
-    bvh_current = bvh_built;
-    bvh_updates.assign(bvh_built.size(), 0);
-    bvh_build_id++;
-    bvh_revision++;
-    return bvh_handle;
-}
-
-void SceneBVH::UpdateObject(Object* obj) {
-    std::lock_guard<std::mutex> lk(bvh_mutex);
-    for (size_t i = 0; i < bvh_objs.size() && i < bvh_current.size(); ++i)
-        if (bvh_objs[i] == obj) {
-            std::memcpy(&bvh_current[i], obj, sizeof(cpt_object));
-            bvh_updates[i]++;
-            bvh_revision++;
-            return;
-        }
-}
-
-void SceneBVH::ReleaseBVH() {
-    std::lock_guard<std::mutex> lk(bvh_mutex);
-    bvh_objs.clear();
-    bvh_seen.clear();
-    bvh_built.clear();
-    bvh_current.clear();
-    bvh_updates.clear();
-    bvh_build_id++;
-    bvh_revision++;
-}
-
-uint64_t SceneBVH::BuildId() {
-    std::lock_guard<std::mutex> lk(bvh_mutex);
-    return bvh_build_id;
-}
-
-uint64_t SceneBVH::Revision() {
-    std::lock_guard<std::mutex> lk(bvh_mutex);
-    return bvh_revision;
-}
-
-void SceneBVH::GetState(uint64_t& build_id, uint64_t& revision, std::vector<cpt_object>* built,
-                        std::vector<cpt_object>& current, std::vector<uint64_t>& updates) {
-    std::lock_guard<std::mutex> lk(bvh_mutex);
-    build_id = bvh_build_id;
-    revision = bvh_revision;
-    if (built) *built = bvh_built;
-    current = bvh_current;
-    updates = bvh_updates;
-}
-
-int SceneBVH::IndexOf(const Object* obj) {
-    std::lock_guard<std::mutex> lk(bvh_mutex);
-    for (size_t i = 0; i < bvh_objs.size(); ++i)
-        if (bvh_objs[i] == obj) return (int)i;
-    return -1;
-}
-
-// ======================================================================================
-// PocaTextureUtils (textures.cu:14-66)
-// ======================================================================================
-static bool load_cptex(const std::string& path, PocaTextureData& t) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return false;
-    char magic[8];
-    uint32_t hdr[4];
-    if (!f.read(magic, 8) || std::memcmp(magic, "CPTTEX01", 8) != 0) return false;
-    if (!f.read(reinterpret_cast<char*>(hdr), sizeof(hdr))) return false;
-    t.width = (int)hdr[0];
-    t.height = (int)hdr[1];
-    t.valid_cols = (int)hdr[2];
-    t.rgba.resize((size_t)t.valid_cols * t.height * 4);
-    return (bool)f.read(reinterpret_cast<char*>(t.rgba.data()), (std::streamsize)t.rgba.size());
-}
-
-static bool load_ppm(const std::string& path, PocaTextureData& t) {
-    std::ifstream f(path, std::ios::binary);
-    if (!f) return false;
-    std::string magic;
-    f >> magic;
-    if (magic != "P6") return false;
-    int w = 0, h = 0, maxv = 0;
-    f >> w >> h >> maxv;
-    f.get();
-    if (w <= 0 || h <= 0 || maxv != 255) return false;
-    std::vector<uint8_t> rgb((size_t)w * h * 3);
-    if (!f.read(reinterpret_cast<char*>(rgb.data()), (std::streamsize)rgb.size())) return false;
-    // textures.cu:32-33: cudaMemcpy2DToArray copies `width` BYTES per row = width/4 texels.
-    t.width = w;
-    t.height = h;
-    t.valid_cols = w / 4;
-    t.rgba.resize((size_t)t.valid_cols * h * 4);
-    for (int y = 0; y < h; ++y)
-        for (int x = 0; x < t.valid_cols; ++x) {
-            const uint8_t* s = &rgb[((size_t)y * w + x) * 3];
-            uint8_t* d = &t.rgba[((size_t)y * t.valid_cols + x) * 4];
-            d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = 255;
-        }
-    return true;
-}
-
-static int address_mode_of(PocaAddressMode m) {
-    switch (m) {
-        case PocaAddressMode::Wrap: return CPT_ADDRESS_WRAP;
-        case PocaAddressMode::Clamp: return CPT_ADDRESS_CLAMP;
-        case PocaAddressMode::Border: return CPT_ADDRESS_BORDER;
-        default: return CPT_ADDRESS_MIRROR;
-    }
-}
-
-PocaTexture PocaTextureUtils::AddTexByFile(std::string file_path, PocaAddressMode addr_mode, PocaFilterMode filter_mode) {
-    PocaTextureData t;
-    t.addr = addr_mode;
-    t.filter = filter_mode;
-    if (!load_cptex(file_path, t) && !load_ppm(file_path, t)) {
-        fprintf(stderr, "[cpt] AddTexByFile: cannot load %s (.cptex or binary PPM)\n", file_path.c_str());
-        return 0;
-    }
-    std::lock_guard<std::mutex> lk(tex_mutex);
-    PocaTexture h = tex_next++;
-    tex_registry[h] = std::move(t);
-    return h;
-}
-
-void PocaTextureUtils::DestroyTexture(PocaTexture tex) {
-    std::lock_guard<std::mutex> lk(tex_mutex);
-    tex_registry.erase(tex);
-}
-
-const PocaTextureData* PocaTextureUtils::Get(PocaTexture tex) {
-    std::lock_guard<std::mutex> lk(tex_mutex);
-    auto it = tex_registry.find(tex);
-    return it == tex_registry.end() ? nullptr : &it->second;
-}
 
 // ======================================================================================
 // PathTracer (path_tracer.cu:29-319)
@@ -292,6 +27,33 @@ static std::string default_sky_path() {
         return dir + "/../assets/sky.cptex";
     }
     return "assets/sky.cptex";
+}
+
+static int address_mode_of(PocaAddressMode m) {
+    switch (m) {
+        case PocaAddressMode::Wrap: return CPT_ADDRESS_WRAP;
+        case PocaAddressMode::Clamp: return CPT_ADDRESS_CLAMP;
+        case PocaAddressMode::Border: return CPT_ADDRESS_BORDER;
+        default: return CPT_ADDRESS_MIRROR;
+    }
+}
+
+static const cpt_camera* as_cpt(const MotionalCamera& cam) { return reinterpret_cast<const cpt_camera*>(&cam); }
+
+// The current camera with its basis computed, as GetCopy() gives it, but from a copy: the
+// camera's own sample index (the display path's Mix weight) does not move for a query.
+static MotionalCamera query_camera(const MotionalCamera& cam) {
+    MotionalCamera c = cam;
+    cpt_camera_get_copy(reinterpret_cast<cpt_camera*>(&c));
+    return c;
+}
+
+// `cam` as FilterRadianceSpatial's records keep it: the basis computed, the sample index (which no
+// first hit depends on) cleared, so that two copies of one camera compare equal byte for byte.
+static MotionalCamera record_camera(const MotionalCamera& cam) {
+    MotionalCamera c = query_camera(cam);
+    c.cur_sample_idx_ = 0;
+    return c;
 }
 
 PathTracer::PathTracer() {}
@@ -495,7 +257,7 @@ bool PathTracer::EnsureFrame(const MotionalCamera& cam) {
             const int rc = n == 1 ? cpt_set_frame(tiles_[r].ctx, cam.width_, cam.height_, nullptr, 0)
                                   : cpt_set_frame(tiles_[r].ctx, cam.width_, cam.height_, rows.data(), (int)rows.size());
             if (rc != CPT_OK) return Fail("cpt_set_frame", tiles_[r].ctx);
-            accum_cam_set_ = gbuffer_known_ = false;   // a fresh frame: no radiance, no G-buffer
+            records_.accum_set = records_.gbuffer_known = false;   // a fresh frame: no radiance, no G-buffer
             tiles_[r].rng_ready = false;
         }
         if (frame_ && cpt_set_frame(frame_, cam.width_, cam.height_, nullptr, 0) != CPT_OK) return Fail("cpt_set_frame", frame_);
@@ -516,55 +278,80 @@ bool PathTracer::EnsureFrame(const MotionalCamera& cam) {
     return true;
 }
 
-// One render of `spp` passes: every tile's launch is queued first (each context's work runs on
-// its own device and stream), then the tiles are gathered into the frame context.
-static MotionalCamera query_camera(const MotionalCamera& cam);
+// The start of every public call that renders or traces at the current camera, in this order: the
+// camera check; the BuildBVH the first such call owes (`build`; ReprojectTracked, which follows
+// edits of an existing build, does not); the camera copy, taken outside mu_ (GetCopy takes the
+// camera's mutex and advances the sample index, a query's copy does neither); mu_, which `lk` holds
+// from here on; the scene and the frame brought to every context.
+bool PathTracer::Begin(const char* who, CameraCopy how, bool build, MotionalCamera& cam, std::unique_lock<std::mutex>& lk) {
+    if (!camera_) {
+        err_ = std::string(who) + ": SetCamera first";
+        return false;
+    }
+    if (build && SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
+    cam = how == CameraCopy::Advance ? camera_->GetCopy() : query_camera(*camera_);
+    lk = std::unique_lock<std::mutex>(mu_);
+    return SyncScene() && EnsureFrame(cam);
+}
 
-// `cam` as FilterRadianceSpatial's records keep it: the basis computed, the sample index (which no
-// first hit depends on) cleared, so that two copies of one camera compare equal byte for byte.
-static MotionalCamera record_camera(const MotionalCamera& cam) {
-    MotionalCamera c = query_camera(cam);
-    c.cur_sample_idx_ = 0;
-    return c;
+bool PathTracer::RequireSingleDevice(const char* who, const char* owned) {
+    if (!frame_) return true;
+    err_ = std::string(who) + ": not available with SetDevices(n > 1), the row tiles own their " + owned;
+    return false;
+}
+
+// A frame exists (and `and_also` holds), or LastError() is `msg`.
+bool PathTracer::HaveFrame(const char* msg, bool and_also) {
+    if (FrameCtx() && width_ != 0 && and_also) return true;
+    err_ = msg;
+    return false;
 }
 
 // The accumulator now belongs to `cam` (FilterRadianceSpatial).
 void PathTracer::NoteAccumCamera(const MotionalCamera& cam) {
-    accum_cam_ = record_camera(cam);
-    accum_cam_set_ = true;
+    records_.accum_cam = record_camera(cam);
+    records_.accum_set = true;
 }
 
 // The first tile's frame G-buffer now holds `cam`'s first hits in the scene as that tile has it.
 void PathTracer::NoteGBuffer(const MotionalCamera& cam) {
-    gbuffer_cam_ = record_camera(cam);
-    gbuffer_rev_ = tiles_[0].scene_rev;
-    gbuffer_known_ = true;
+    records_.gbuffer_cam = record_camera(cam);
+    records_.gbuffer_rev = tiles_[0].scene_rev;
+    records_.gbuffer_known = true;
 }
 
-bool PathTracer::RenderPass(MotionalCamera& cam, int spp, bool accumulate) {
-    if (!SyncScene() || !EnsureFrame(cam)) return false;
-    NoteAccumCamera(cam);
-    // many passes per pixel: heaviest tiles first (same image, shorter tail)
-    // few passes (the DispatchRay loop): heaviest tiles first by the previous pass's work, no pilot
-    const uint32_t flags = CPT_RENDER_AUX | (accumulate ? CPT_RENDER_ACCUMULATE : 0u) |
-                           (ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) |
-                           (spp >= 64 ? CPT_SCHEDULE_COST : CPT_SCHEDULE_PREVIOUS);
-    if (!frame_) {
-        if (cpt_render(tiles_[0].ctx, reinterpret_cast<const cpt_camera*>(&cam), spp, (int)max_recursion_depth_,
-                       flags | CPT_RENDER_SYNC) != CPT_OK)
-            return Fail("cpt_render", tiles_[0].ctx);
-        return true;
-    }
-    for (Tile& t : tiles_)
-        if (cpt_render(t.ctx, reinterpret_cast<const cpt_camera*>(&cam), spp, (int)max_recursion_depth_, flags) != CPT_OK)
-            return Fail("cpt_render", t.ctx);
-    // every gather queues behind its tile's render (events, no host wait); one wait at the end
+// The row tiles into the frame context: every gather queues behind its tile's render (events, no
+// host wait); one wait at the end.
+bool PathTracer::GatherTiles() {
     for (Tile& t : tiles_)
         if (cpt_gather_rows(frame_, t.ctx) != CPT_OK) return Fail("cpt_gather_rows", frame_);
     if (cpt_synchronize(frame_) != CPT_OK) return Fail("cpt_synchronize", frame_);
     for (Tile& t : tiles_)   // the tiles' device errors (their work is done by now)
         if (cpt_synchronize(t.ctx) != CPT_OK) return Fail("cpt_synchronize", t.ctx);
     return true;
+}
+
+// One render call, `launch(ctx, extra flags)`, named `what` to Fail: synchronous on the single
+// context; with row tiles every tile's launch is queued first (each context's work runs on its own
+// device and stream), then the tiles are gathered into the frame context.
+template <class Launch>
+bool PathTracer::LaunchOnTiles(const char* what, Launch launch) {
+    if (!frame_) return launch(tiles_[0].ctx, (uint32_t)CPT_RENDER_SYNC) == CPT_OK || Fail(what, tiles_[0].ctx);
+    for (Tile& t : tiles_)
+        if (launch(t.ctx, 0u) != CPT_OK) return Fail(what, t.ctx);
+    return GatherTiles();
+}
+
+// One render of `spp` passes at `cam`, the scene and the frame being on every context.
+bool PathTracer::RenderPass(MotionalCamera& cam, int spp, bool accumulate) {
+    NoteAccumCamera(cam);
+    // heaviest tiles first (same image, shorter tail): many passes per pixel by a cost pilot, few (the
+    // DispatchRay loop) by the previous pass's work, no pilot
+    const uint32_t flags = CPT_RENDER_AUX | (accumulate ? CPT_RENDER_ACCUMULATE : 0u) | WalkFlags() |
+                           (spp >= 64 ? CPT_SCHEDULE_COST : CPT_SCHEDULE_PREVIOUS);
+    return LaunchOnTiles("cpt_render", [&](cpt_ctx* ctx, uint32_t extra) {
+        return cpt_render(ctx, as_cpt(cam), spp, (int)max_recursion_depth_, flags | extra);
+    });
 }
 
 void PathTracer::InitPipeline() {
@@ -603,10 +390,10 @@ void PathTracer::PipelineLoop() {
         bool ok;
         {
             std::lock_guard<std::mutex> lk(mu_);
-            if (display_reproject_) {
+            if (loop_.reproject) {
                 ok = DisplayPassWithHistory(cma);
             } else {
-                ok = RenderPass(cma, 1, false);
+                ok = SyncScene() && EnsureFrame(cma) && RenderPass(cma, 1, false);
                 if (ok && cpt_denoise_mix(FrameCtx(), cma.cur_sample_idx_, output_buffer_.data()) != CPT_OK)
                     ok = Fail("cpt_denoise_mix");
             }
@@ -623,12 +410,38 @@ bool PathTracer::SetDisplayReprojection(bool on, int max_history, float plane_to
                std::to_string(plane_tol) + " (finite, >= 0)";
         return false;
     }
-    display_reproject_ = on;
-    display_through_edits_ = on && through_edits;
-    loop_history_ = false;   // whatever history the context holds is not this loop's
-    display_max_history_ = max_history;
-    display_plane_tol_ = plane_tol;
-    prev_pass_ = false;   // the first pass after a switch restarts
+    loop_.reproject = on;
+    loop_.through_edits = on && through_edits;
+    ForgetLoopHistory();   // whatever history the context holds is not this loop's
+    loop_.max_history = max_history;
+    loop_.plane_tol = plane_tol;
+    loop_.prev_pass = false;   // the first pass after a switch restarts
+    return true;
+}
+
+// (a frame under 16 pixels either way has no launch region: no display pass ever ran there)
+bool PathTracer::PrevFits(bool had_prev) const {
+    return had_prev && loop_.prev_cam.width_ == width_ && loop_.prev_cam.height_ == height_ && width_ >= 16 && height_ >= 16 &&
+           !frame_;
+}
+
+// through_edits.  The context's captured history serves this loop only while it is the previous
+// pass's: captured or renewed by this loop (loop_.history; Reproject, CaptureHistory,
+// ReprojectTracked and SetDisplayReprojection clear it, the untracked C calls drop the capture
+// itself), at the scene revision of the previous pass, and at a camera that equals prev_cam in
+// every field but the sample index.  Anything else is not trusted: the history is captured anew
+// at the previous pass's camera where the context still holds that pass's scene, and the display
+// restarts where it does not.  False: cpt_history_info failed.
+bool PathTracer::HistoryIsPrev(cpt_ctx* ctx, bool& is_prev) const {
+    int valid = 0;
+    cpt_camera cam;
+    is_prev = false;
+    if (cpt_history_info(ctx, &valid, &cam) != CPT_OK) return false;
+    if (valid && loop_.history && loop_.history_rev == loop_.prev_rev) {
+        cpt_camera prev = *as_cpt(loop_.prev_cam);
+        prev.cur_sample_idx = cam.cur_sample_idx;
+        is_prev = std::memcmp(&prev, &cam, sizeof(cam)) == 0;
+    }
     return true;
 }
 
@@ -639,90 +452,80 @@ bool PathTracer::SetDisplayReprojection(bool on, int max_history, float plane_to
 // loop's first pass is such a one, its index being 2 after InitBuffers' copy (path_tracer.cu:258),
 // so a still camera's frames are the reference loop's.
 bool PathTracer::DisplayPassWithHistory(MotionalCamera& cma) {
-    const bool had_prev = prev_pass_, refreshed = cma.cur_sample_idx_ == 1;
-    prev_pass_ = false;
-    const uint32_t walk = ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u;
-    // (a frame under 16 pixels either way has no launch region: no display pass ever ran there)
-    auto prev_fits = [&] {
-        return had_prev && prev_cam_.width_ == width_ && prev_cam_.height_ == height_ && width_ >= 16 && height_ >= 16 && !frame_;
-    };
-    // through_edits.  The context's captured history serves this loop only while it is the previous
-    // pass's: captured or renewed by this loop (loop_history_; Reproject, CaptureHistory,
-    // ReprojectTracked and SetDisplayReprojection clear it, the untracked C calls drop the capture
-    // itself), at the scene revision of the previous pass, and at a camera that equals prev_cam_ in
-    // every field but the sample index.  Anything else is not trusted: the history is captured anew
-    // at the previous pass's camera where the context still holds that pass's scene, and the display
-    // restarts where it does not.
-    if (!had_prev) loop_history_ = false;
-    auto history_is_prev = [&](cpt_ctx* ctx, bool& is_prev) {
-        int valid = 0;
-        cpt_camera cam;
-        is_prev = false;
-        if (cpt_history_info(ctx, &valid, &cam) != CPT_OK) return false;
-        if (valid && loop_history_ && loop_history_rev_ == prev_scene_rev_) {
-            cpt_camera prev = *reinterpret_cast<const cpt_camera*>(&prev_cam_);
-            prev.cur_sample_idx = cam.cur_sample_idx;
-            is_prev = std::memcmp(&prev, &cam, sizeof(cam)) == 0;
-        }
-        return true;
-    };
-    // A move or an edit is about to reach the context: capture before SyncScene lets it.  (Revision()
-    // is read before SyncScene reads it again: an UpdateObject from another thread that lands
-    // between the two is not seen here, no capture is made for it, and the pass below then finds an
-    // edited scene without a history of the previous pass and restarts the display.  Safe, but a
-    // restart that through_edits would otherwise have avoided.)
-    if (display_through_edits_ && prev_fits() && !tiles_.empty() && tiles_[0].scene_synced &&
-        (refreshed || SceneBVH::Revision() != tiles_[0].scene_rev || tiles_[0].scene_rev != prev_scene_rev_)) {
+    const bool had_prev = loop_.prev_pass, refreshed = cma.cur_sample_idx_ == 1;
+    loop_.prev_pass = false;
+    if (!had_prev) ForgetLoopHistory();
+    return CaptureBeforeEdit(had_prev, refreshed) && SyncScene() && EnsureFrame(cma) && MoveDisplay(cma, had_prev, refreshed) &&
+           PassAndMix(cma, !refreshed && !had_prev);
+}
+
+// A move or an edit is about to reach the context: capture before SyncScene lets it.  (Revision()
+// is read before SyncScene reads it again: an UpdateObject from another thread that lands
+// between the two is not seen here, no capture is made for it, and the pass below then finds an
+// edited scene without a history of the previous pass and restarts the display.  Safe, but a
+// restart that through_edits would otherwise have avoided.)
+bool PathTracer::CaptureBeforeEdit(bool had_prev, bool refreshed) {
+    if (loop_.through_edits && PrevFits(had_prev) && !tiles_.empty() && tiles_[0].scene_synced &&
+        (refreshed || SceneBVH::Revision() != tiles_[0].scene_rev || tiles_[0].scene_rev != loop_.prev_rev)) {
         cpt_ctx* ctx = tiles_[0].ctx;
         bool is_prev = false;
-        if (!history_is_prev(ctx, is_prev)) return Fail("cpt_history_info", ctx);
+        if (!HistoryIsPrev(ctx, is_prev)) return Fail("cpt_history_info", ctx);
         if (!is_prev) {
-            loop_history_ = false;
+            ForgetLoopHistory();
             // (edits another call already brought to the context cannot be captured behind)
-            if (tiles_[0].scene_build == prev_scene_build_ && tiles_[0].scene_rev == prev_scene_rev_) {
-                gbuffer_known_ = false;   // the capture traces the frame's G-buffer
-                if (cpt_history_capture(ctx, reinterpret_cast<const cpt_camera*>(&prev_cam_), walk) != CPT_OK)
-                    return Fail("cpt_history_capture", ctx);
-                loop_history_ = true;
-                loop_history_rev_ = prev_scene_rev_;
+            if (tiles_[0].scene_build == loop_.prev_build && tiles_[0].scene_rev == loop_.prev_rev) {
+                records_.gbuffer_known = false;   // the capture traces the frame's G-buffer
+                if (cpt_history_capture(ctx, as_cpt(loop_.prev_cam), WalkFlags()) != CPT_OK) return Fail("cpt_history_capture", ctx);
+                loop_.history = true;
+                loop_.history_rev = loop_.prev_rev;
             }
         }
     }
-    if (!SyncScene() || !EnsureFrame(cma)) return false;
+    return true;
+}
+
+// After a Refresh or (through_edits) an edit of the same build, the scene being on the context: the
+// display state moves to `cma`, or restarts where it cannot.
+bool PathTracer::MoveDisplay(const MotionalCamera& cma, bool had_prev, bool refreshed) {
     const Tile& t0 = tiles_[0];
-    const bool same_build = t0.scene_build == prev_scene_build_, same_rev = t0.scene_rev == prev_scene_rev_;
-    const bool edited = display_through_edits_ && had_prev && same_build && !same_rev;
-    if (refreshed || edited) {
-        bool carry = prev_fits() && same_build && (same_rev || display_through_edits_);
-        if (carry && display_through_edits_) {
-            // dropped by a new frame or scene, never captured, or not the previous pass's: restart
-            if (!history_is_prev(t0.ctx, carry)) return Fail("cpt_history_info", t0.ctx);
-        }
-        if (carry) gbuffer_known_ = false;   // both reprojection calls trace the frame's G-buffer
-        if (carry && display_through_edits_) {
-            if (cpt_reproject_display_tracked(t0.ctx, reinterpret_cast<const cpt_camera*>(&cma), display_max_history_,
-                                              display_plane_tol_, walk) != CPT_OK)
-                return Fail("cpt_reproject_display_tracked", t0.ctx);
-            loop_history_rev_ = t0.scene_rev;   // the call renewed the history: cma, the current objects
-        } else if (carry) {
-            if (cpt_reproject_display(t0.ctx, reinterpret_cast<const cpt_camera*>(&prev_cam_), reinterpret_cast<const cpt_camera*>(&cma),
-                                      display_max_history_, display_plane_tol_, walk) != CPT_OK)
-                return Fail("cpt_reproject_display", t0.ctx);
-        } else {
-            loop_history_ = false;
-            if (cpt_reset_display(FrameCtx()) != CPT_OK) return Fail("cpt_reset_display");
-        }
+    const bool same_build = t0.scene_build == loop_.prev_build, same_rev = t0.scene_rev == loop_.prev_rev;
+    const bool edited = loop_.through_edits && had_prev && same_build && !same_rev;
+    if (!refreshed && !edited) return true;
+    bool carry = PrevFits(had_prev) && same_build && (same_rev || loop_.through_edits);
+    if (carry && loop_.through_edits) {
+        // dropped by a new frame or scene, never captured, or not the previous pass's: restart
+        if (!HistoryIsPrev(t0.ctx, carry)) return Fail("cpt_history_info", t0.ctx);
     }
-    if (!RenderPass(cma, 1, false)) return false;
-    if (!refreshed && !had_prev) {
+    if (carry) records_.gbuffer_known = false;   // both reprojection calls trace the frame's G-buffer
+    if (carry && loop_.through_edits) {
+        if (cpt_reproject_display_tracked(t0.ctx, as_cpt(cma), loop_.max_history, loop_.plane_tol, WalkFlags()) != CPT_OK)
+            return Fail("cpt_reproject_display_tracked", t0.ctx);
+        loop_.history_rev = t0.scene_rev;   // the call renewed the history: cma, the current objects
+    } else if (carry) {
+        if (cpt_reproject_display(t0.ctx, as_cpt(loop_.prev_cam), as_cpt(cma), loop_.max_history, loop_.plane_tol, WalkFlags()) !=
+            CPT_OK)
+            return Fail("cpt_reproject_display", t0.ctx);
+    } else {
+        ForgetLoopHistory();
+        if (cpt_reset_display(FrameCtx()) != CPT_OK) return Fail("cpt_reset_display");
+    }
+    return true;
+}
+
+// The pass (with the sync every pass of the loop starts with: an edit that landed since the one
+// above reaches the context here), the Mix, joining the loop's mean so far at the camera's index
+// (`join_mean`) or per pixel, and the record of this pass for the next.
+bool PathTracer::PassAndMix(MotionalCamera& cma, bool join_mean) {
+    if (!SyncScene() || !EnsureFrame(cma) || !RenderPass(cma, 1, false)) return false;
+    if (join_mean) {
         if (cpt_denoise_mix(FrameCtx(), cma.cur_sample_idx_, output_buffer_.data()) != CPT_OK) return Fail("cpt_denoise_mix");
     } else if (cpt_denoise_mix_history(FrameCtx(), output_buffer_.data()) != CPT_OK) {
         return Fail("cpt_denoise_mix_history");
     }
-    prev_cam_ = cma;
-    prev_scene_build_ = tiles_[0].scene_build;
-    prev_scene_rev_ = tiles_[0].scene_rev;
-    prev_pass_ = true;
+    loop_.prev_cam = cma;
+    loop_.prev_build = tiles_[0].scene_build;
+    loop_.prev_rev = tiles_[0].scene_rev;
+    loop_.prev_pass = true;
     return true;
 }
 
@@ -733,44 +536,22 @@ void PathTracer::Stop() {
 }
 
 bool PathTracer::Render(int spp, bool accumulate) {
-    if (!camera_) {
-        err_ = "Render: SetCamera first";
-        return false;
-    }
-    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
-    MotionalCamera cma = camera_->GetCopy();
-    std::lock_guard<std::mutex> lk(mu_);
-    return RenderPass(cma, spp, accumulate);
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    return Begin("Render", CameraCopy::Advance, true, cam, lk) && RenderPass(cam, spp, accumulate);
 }
 
 // Top-up render (cpt_render_to_count): as RenderPass, every row tile on its own
 // accumulator, then the gather.
 bool PathTracer::RenderToCount(int target) {
-    if (!camera_) {
-        err_ = "RenderToCount: SetCamera first";
-        return false;
-    }
-    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
-    MotionalCamera cam = camera_->GetCopy();
-    std::lock_guard<std::mutex> lk(mu_);
-    if (!SyncScene() || !EnsureFrame(cam)) return false;
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("RenderToCount", CameraCopy::Advance, true, cam, lk)) return false;
     NoteAccumCamera(cam);
-    const uint32_t flags = CPT_RENDER_AUX | (ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u);
-    const cpt_camera* c = reinterpret_cast<const cpt_camera*>(&cam);
-    if (!frame_) {
-        if (cpt_render_to_count(tiles_[0].ctx, c, target, (int)max_recursion_depth_, flags | CPT_RENDER_SYNC) != CPT_OK)
-            return Fail("cpt_render_to_count", tiles_[0].ctx);
-        return true;
-    }
-    for (Tile& t : tiles_)
-        if (cpt_render_to_count(t.ctx, c, target, (int)max_recursion_depth_, flags) != CPT_OK)
-            return Fail("cpt_render_to_count", t.ctx);
-    for (Tile& t : tiles_)
-        if (cpt_gather_rows(frame_, t.ctx) != CPT_OK) return Fail("cpt_gather_rows", frame_);
-    if (cpt_synchronize(frame_) != CPT_OK) return Fail("cpt_synchronize", frame_);
-    for (Tile& t : tiles_)   // the tiles' device errors (their work is done by now)
-        if (cpt_synchronize(t.ctx) != CPT_OK) return Fail("cpt_synchronize", t.ctx);
-    return true;
+    const uint32_t flags = CPT_RENDER_AUX | WalkFlags();
+    return LaunchOnTiles("cpt_render_to_count", [&](cpt_ctx* ctx, uint32_t extra) {
+        return cpt_render_to_count(ctx, as_cpt(cam), target, (int)max_recursion_depth_, flags | extra);
+    });
 }
 
 // The adaptive render over row tiles: every tile's first round is queued, then this thread goes
@@ -791,8 +572,8 @@ bool PathTracer::RenderAdaptiveTiles(MotionalCamera& cam, int min_spp, int max_s
         return false;
     };
     for (size_t i = 0; i < n; ++i) {
-        if (cpt_adaptive_begin(tiles_[i].ctx, reinterpret_cast<const cpt_camera*>(&cam), min_spp, max_spp, batch, rel_error,
-                               (int)max_recursion_depth_, flags) != CPT_OK)
+        if (cpt_adaptive_begin(tiles_[i].ctx, as_cpt(cam), min_spp, max_spp, batch, rel_error, (int)max_recursion_depth_, flags) !=
+            CPT_OK)
             return fail_all("cpt_adaptive_begin", tiles_[i].ctx);
         pending[i] = 1;
     }
@@ -809,13 +590,10 @@ bool PathTracer::RenderAdaptiveTiles(MotionalCamera& cam, int min_spp, int max_s
                 --left;
             }
         }
-    for (Tile& t : tiles_)
-        if (cpt_gather_rows(frame_, t.ctx) != CPT_OK) return Fail("cpt_gather_rows", frame_);
-    if (cpt_synchronize(frame_) != CPT_OK) return Fail("cpt_synchronize", frame_);
+    if (!GatherTiles()) return false;
     int most = 0;
     uint64_t sum = 0;
-    for (Tile& t : tiles_) {
-        if (cpt_synchronize(t.ctx) != CPT_OK) return Fail("cpt_synchronize", t.ctx);
+    for (Tile& t : tiles_) {   // (each tile synchronised by the gather)
         int r = 0;
         uint64_t p = 0;
         if (cpt_adaptive_info(t.ctx, &r, nullptr, 0, &p) != CPT_OK) return Fail("cpt_adaptive_info", t.ctx);
@@ -829,21 +607,14 @@ bool PathTracer::RenderAdaptiveTiles(MotionalCamera& cam, int min_spp, int max_s
 
 bool PathTracer::RenderAdaptive(int min_spp, int max_spp, int batch, float rel_error, int* rounds,
                                 uint64_t* passes_done) {
-    if (!camera_) {
-        err_ = "RenderAdaptive: SetCamera first";
-        return false;
-    }
-    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
-    MotionalCamera cma = camera_->GetCopy();
-    std::lock_guard<std::mutex> lk(mu_);
-    if (!SyncScene() || !EnsureFrame(cma)) return false;
+    MotionalCamera cma;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("RenderAdaptive", CameraCopy::Advance, true, cma, lk)) return false;
     NoteAccumCamera(cma);   // for the row tiles too (RenderAdaptiveTiles)
-    const uint32_t flags = CPT_RENDER_AUX | (ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) |
-                           (max_spp >= 64 ? CPT_SCHEDULE_COST : 0u);
+    const uint32_t flags = CPT_RENDER_AUX | WalkFlags() | (max_spp >= 64 ? CPT_SCHEDULE_COST : 0u);
     if (frame_) return RenderAdaptiveTiles(cma, min_spp, max_spp, batch, rel_error, flags, rounds, passes_done);
     cpt_ctx* ctx = tiles_[0].ctx;
-    if (cpt_render_adaptive(ctx, reinterpret_cast<const cpt_camera*>(&cma), min_spp, max_spp, batch, rel_error,
-                            (int)max_recursion_depth_, flags) != CPT_OK)
+    if (cpt_render_adaptive(ctx, as_cpt(cma), min_spp, max_spp, batch, rel_error, (int)max_recursion_depth_, flags) != CPT_OK)
         return Fail("cpt_render_adaptive", ctx);
     if (cpt_adaptive_info(ctx, rounds, nullptr, 0, passes_done) != CPT_OK) return Fail("cpt_adaptive_info", ctx);
     return true;
@@ -851,42 +622,30 @@ bool PathTracer::RenderAdaptive(int min_spp, int max_spp, int batch, float rel_e
 
 bool PathTracer::ReadNoise(float* rel) {
     std::lock_guard<std::mutex> lk(mu_);
-    if (!FrameCtx() || width_ == 0) {
-        err_ = "ReadNoise: RenderAdaptive first";
-        return false;
-    }
+    if (!HaveFrame("ReadNoise: RenderAdaptive first")) return false;
     if (cpt_read_noise(FrameCtx(), rel, (size_t)width_ * height_) != CPT_OK) return Fail("cpt_read_noise");
     return true;
 }
 
 bool PathTracer::FilterRadiance(int levels, float sigma_l, int sharpness) {
     std::lock_guard<std::mutex> lk(mu_);
-    if (!FrameCtx() || width_ == 0) {
-        err_ = "FilterRadiance: RenderAdaptive first";
-        return false;
-    }
+    if (!HaveFrame("FilterRadiance: RenderAdaptive first")) return false;
     if (cpt_filter_frame(FrameCtx(), levels, sigma_l, sharpness) != CPT_OK) return Fail("cpt_filter_frame");
     return true;
 }
 
 bool PathTracer::FilterRadianceSpatial(int levels, float sigma_l, int sharpness) {
     std::lock_guard<std::mutex> lk(mu_);
-    if (tiles_.empty() || width_ == 0 || !accum_cam_set_) {
-        err_ = "FilterRadianceSpatial: Render first";
-        return false;
-    }
-    if (frame_) {
-        err_ = "FilterRadianceSpatial: not available with SetDevices(n > 1), the row tiles own their G-buffers";
-        return false;
-    }
+    if (!HaveFrame("FilterRadianceSpatial: Render first", records_.accum_set)) return false;
+    if (!RequireSingleDevice("FilterRadianceSpatial", "G-buffers")) return false;
     cpt_ctx* ctx = tiles_[0].ctx;
     // the G-buffer the context holds is reused only if it is the accumulator's camera's, in the
     // scene the context has now
-    if (!gbuffer_known_ || gbuffer_rev_ != tiles_[0].scene_rev || std::memcmp(&gbuffer_cam_, &accum_cam_, sizeof(accum_cam_)) != 0) {
-        gbuffer_known_ = false;
-        if (cpt_gbuffer(ctx, reinterpret_cast<const cpt_camera*>(&accum_cam_), ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK)
-            return Fail("cpt_gbuffer", ctx);
-        NoteGBuffer(accum_cam_);
+    if (!records_.gbuffer_known || records_.gbuffer_rev != tiles_[0].scene_rev ||
+        std::memcmp(&records_.gbuffer_cam, &records_.accum_cam, sizeof(records_.accum_cam)) != 0) {
+        records_.gbuffer_known = false;
+        if (cpt_gbuffer(ctx, as_cpt(records_.accum_cam), WalkFlags()) != CPT_OK) return Fail("cpt_gbuffer", ctx);
+        NoteGBuffer(records_.accum_cam);
     }
     if (cpt_filter_frame_spatial(ctx, levels, sigma_l, sharpness) != CPT_OK) return Fail("cpt_filter_frame_spatial", ctx);
     return true;
@@ -894,10 +653,7 @@ bool PathTracer::FilterRadianceSpatial(int levels, float sigma_l, int sharpness)
 
 bool PathTracer::ReadFiltered(std::vector<float>& rgb) {
     std::lock_guard<std::mutex> lk(mu_);
-    if (!FrameCtx() || width_ == 0) {
-        err_ = "ReadFiltered: FilterRadiance first";
-        return false;
-    }
+    if (!HaveFrame("ReadFiltered: FilterRadiance first")) return false;
     rgb.resize((size_t)width_ * height_ * 3);
     if (cpt_read_filtered(FrameCtx(), rgb.data(), nullptr, (size_t)width_ * height_) != CPT_OK)
         return Fail("cpt_read_filtered");
@@ -906,10 +662,7 @@ bool PathTracer::ReadFiltered(std::vector<float>& rgb) {
 
 bool PathTracer::ReadRadiance(std::vector<float>& rgb) {
     std::lock_guard<std::mutex> lk(mu_);
-    if (!FrameCtx() || width_ == 0) {
-        err_ = "ReadRadiance: nothing rendered";
-        return false;
-    }
+    if (!HaveFrame("ReadRadiance: nothing rendered")) return false;
     std::vector<float> acc((size_t)width_ * height_ * 4);
     if (cpt_read_accum(FrameCtx(), acc.data()) != CPT_OK) return Fail("cpt_read_accum");
     rgb.resize((size_t)width_ * height_ * 3);
@@ -928,51 +681,36 @@ bool PathTracer::ReadFrameBGRA(std::vector<uint8_t>& bgra) {
     return !bgra.empty();
 }
 
-static bool write_pfm(const std::string& path, const std::vector<float>& rgb, int width, int height) {
+// `rgb` as a PFM file; where it cannot be written, `err` is `who`'s message.
+static bool write_pfm(const char* who, const std::string& path, const std::vector<float>& rgb, int width, int height,
+                      std::string& err) {
     std::ofstream f(path, std::ios::binary);
-    if (!f) return false;
-    f << "PF\n" << width << " " << height << "\n-1.0\n";
-    for (int y = height - 1; y >= 0; --y)   // PFM rows are bottom-to-top
-        f.write(reinterpret_cast<const char*>(&rgb[(size_t)y * width * 3]), (std::streamsize)width * 3 * sizeof(float));
-    return (bool)f;
+    if (f) {
+        f << "PF\n" << width << " " << height << "\n-1.0\n";
+        for (int y = height - 1; y >= 0; --y)   // PFM rows are bottom-to-top
+            f.write(reinterpret_cast<const char*>(&rgb[(size_t)y * width * 3]), (std::streamsize)width * 3 * sizeof(float));
+        if (f) return true;
+    }
+    err = std::string(who) + ": cannot write " + path;
+    return false;
 }
 
 bool PathTracer::SaveRadiancePFM(const std::string& path) {
     std::vector<float> rgb;
-    if (!ReadRadiance(rgb)) return false;
-    if (write_pfm(path, rgb, width_, height_)) return true;
-    err_ = "SaveRadiancePFM: cannot write " + path;
-    return false;
+    return ReadRadiance(rgb) && write_pfm("SaveRadiancePFM", path, rgb, width_, height_, err_);
 }
 
 bool PathTracer::SaveFilteredPFM(const std::string& path) {
     std::vector<float> rgb;
-    if (!ReadFiltered(rgb)) return false;
-    if (write_pfm(path, rgb, width_, height_)) return true;
-    err_ = "SaveFilteredPFM: cannot write " + path;
-    return false;
-}
-
-// The current camera with its basis computed, as GetCopy() gives it, but from a copy: the
-// camera's own sample index (the display path's Mix weight) does not move for a query.
-static MotionalCamera query_camera(const MotionalCamera& cam) {
-    MotionalCamera c = cam;
-    cpt_camera_get_copy(reinterpret_cast<cpt_camera*>(&c));
-    return c;
+    return ReadFiltered(rgb) && write_pfm("SaveFilteredPFM", path, rgb, width_, height_, err_);
 }
 
 int PathTracer::Pick(int x, int y, float* t) {
-    if (!camera_) {
-        err_ = "Pick: SetCamera first";
-        return -1;
-    }
-    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
-    const MotionalCamera cma = query_camera(*camera_);
-    std::lock_guard<std::mutex> lk(mu_);
-    if (!SyncScene() || !EnsureFrame(cma)) return -1;
+    MotionalCamera cma;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("Pick", CameraCopy::Query, true, cma, lk)) return -1;
     int32_t object = -1;
-    if (cpt_pick(tiles_[0].ctx, reinterpret_cast<const cpt_camera*>(&cma), x, y, ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u,
-                 &object, t) != CPT_OK) {
+    if (cpt_pick(tiles_[0].ctx, as_cpt(cma), x, y, WalkFlags(), &object, t) != CPT_OK) {
         Fail("cpt_pick", tiles_[0].ctx);
         return -1;
     }
@@ -982,19 +720,12 @@ int PathTracer::Pick(int x, int y, float* t) {
 // Every tile's G-buffer is queued first, then each is read into its rows of the frame.
 bool PathTracer::ReadGBuffer(std::vector<int32_t>& id, std::vector<float>& t, std::vector<float>& normal3,
                              std::vector<float>& albedo3) {
-    if (!camera_) {
-        err_ = "ReadGBuffer: SetCamera first";
-        return false;
-    }
-    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
-    const MotionalCamera cma = query_camera(*camera_);
-    std::lock_guard<std::mutex> lk(mu_);
-    if (!SyncScene() || !EnsureFrame(cma)) return false;
-    const uint32_t flags = ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u;
-    gbuffer_known_ = false;
+    MotionalCamera cma;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("ReadGBuffer", CameraCopy::Query, true, cma, lk)) return false;
+    records_.gbuffer_known = false;
     for (Tile& tile : tiles_)
-        if (cpt_gbuffer(tile.ctx, reinterpret_cast<const cpt_camera*>(&cma), flags) != CPT_OK)
-            return Fail("cpt_gbuffer", tile.ctx);
+        if (cpt_gbuffer(tile.ctx, as_cpt(cma), WalkFlags()) != CPT_OK) return Fail("cpt_gbuffer", tile.ctx);
     NoteGBuffer(cma);
     const size_t w = (size_t)width_, npix = w * height_;
     id.resize(npix);
@@ -1018,83 +749,60 @@ bool PathTracer::ReadGBuffer(std::vector<int32_t>& id, std::vector<float>& t, st
         ta.resize(3 * m);
         if (cpt_read_gbuffer(tiles_[r].ctx, tid.data(), tt.data(), tn.data(), ta.data(), m) != CPT_OK)
             return Fail("cpt_read_gbuffer", tiles_[r].ctx);
-        for (size_t k = 0; k < rows.size(); ++k) {
-            const size_t dst = (size_t)rows[k] * w, src = k * w;
-            std::copy(tid.begin() + src, tid.begin() + src + w, id.begin() + dst);
-            std::copy(tt.begin() + src, tt.begin() + src + w, t.begin() + dst);
-            std::copy(tn.begin() + 3 * src, tn.begin() + 3 * (src + w), normal3.begin() + 3 * dst);
-            std::copy(ta.begin() + 3 * src, ta.begin() + 3 * (src + w), albedo3.begin() + 3 * dst);
-        }
+        // the tile's k-th row of a plane of `c` components per pixel to the frame's row rows[k]
+        auto scatter = [&](const auto& tile_plane, auto& plane, size_t c) {
+            for (size_t k = 0; k < rows.size(); ++k)
+                std::copy(tile_plane.begin() + c * k * w, tile_plane.begin() + c * (k + 1) * w, plane.begin() + c * rows[k] * w);
+        };
+        scatter(tid, id, 1);
+        scatter(tt, t, 1);
+        scatter(tn, normal3, 3);
+        scatter(ta, albedo3, 3);
     }
     return true;
 }
 
 bool PathTracer::Reproject(const MotionalCamera& from, int max_history, float plane_tol) {
-    if (!camera_) {
-        err_ = "Reproject: SetCamera first";
-        return false;
-    }
-    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
-    const MotionalCamera to = query_camera(*camera_), old = query_camera(from);
-    std::lock_guard<std::mutex> lk(mu_);
-    if (!SyncScene() || !EnsureFrame(to)) return false;
-    if (frame_) {
-        err_ = "Reproject: not available with SetDevices(n > 1), the row tiles own their accumulators";
-        return false;
-    }
+    const MotionalCamera old = query_camera(from);
+    MotionalCamera to;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("Reproject", CameraCopy::Query, true, to, lk) || !RequireSingleDevice("Reproject", "accumulators")) return false;
     cpt_ctx* ctx = tiles_[0].ctx;
-    if (cpt_reproject_accum(ctx, reinterpret_cast<const cpt_camera*>(&old), reinterpret_cast<const cpt_camera*>(&to), max_history,
-                            plane_tol, ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK ||
+    if (cpt_reproject_accum(ctx, as_cpt(old), as_cpt(to), max_history, plane_tol, WalkFlags()) != CPT_OK ||
         cpt_synchronize(ctx) != CPT_OK)
         return Fail("cpt_reproject_accum", ctx);
     NoteAccumCamera(to);
     NoteGBuffer(to);
-    loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
+    ForgetLoopHistory();
     return true;
 }
 
 bool PathTracer::CaptureHistory() {
-    if (!camera_) {
-        err_ = "CaptureHistory: SetCamera first";
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("CaptureHistory", CameraCopy::Query, true, cam, lk) || !RequireSingleDevice("CaptureHistory", "accumulators"))
         return false;
-    }
-    if (SceneBVH::BuildId() == 0) SceneBVH::BuildBVH();
-    const MotionalCamera cam = query_camera(*camera_);
-    std::lock_guard<std::mutex> lk(mu_);
-    if (!SyncScene() || !EnsureFrame(cam)) return false;
-    if (frame_) {
-        err_ = "CaptureHistory: not available with SetDevices(n > 1), the row tiles own their accumulators";
-        return false;
-    }
     cpt_ctx* ctx = tiles_[0].ctx;
-    gbuffer_known_ = false;
-    if (cpt_history_capture(ctx, reinterpret_cast<const cpt_camera*>(&cam), ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK)
-        return Fail("cpt_history_capture", ctx);
+    records_.gbuffer_known = false;
+    if (cpt_history_capture(ctx, as_cpt(cam), WalkFlags()) != CPT_OK) return Fail("cpt_history_capture", ctx);
     NoteGBuffer(cam);
-    loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
+    ForgetLoopHistory();
     return true;
 }
 
 bool PathTracer::ReprojectTracked(int max_history, float plane_tol) {
-    if (!camera_) {
-        err_ = "ReprojectTracked: SetCamera first";
+    MotionalCamera to;
+    std::unique_lock<std::mutex> lk;
+    // (no BuildBVH; the pending UpdateObjects are refit by Begin's sync)
+    if (!Begin("ReprojectTracked", CameraCopy::Query, false, to, lk) || !RequireSingleDevice("ReprojectTracked", "accumulators"))
         return false;
-    }
-    const MotionalCamera to = query_camera(*camera_);
-    std::lock_guard<std::mutex> lk(mu_);
-    if (!SyncScene() || !EnsureFrame(to)) return false;   // the pending UpdateObjects are refit here
-    if (frame_) {
-        err_ = "ReprojectTracked: not available with SetDevices(n > 1), the row tiles own their accumulators";
-        return false;
-    }
     cpt_ctx* ctx = tiles_[0].ctx;
-    if (cpt_reproject_accum_tracked(ctx, reinterpret_cast<const cpt_camera*>(&to), max_history, plane_tol,
-                                    ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u) != CPT_OK ||
+    if (cpt_reproject_accum_tracked(ctx, as_cpt(to), max_history, plane_tol, WalkFlags()) != CPT_OK ||
         cpt_synchronize(ctx) != CPT_OK)
         return Fail("cpt_reproject_accum_tracked", ctx);
     NoteAccumCamera(to);
     NoteGBuffer(to);
-    loop_history_ = false;   // the context's history is no longer the DispatchRay loop's
+    ForgetLoopHistory();
     return true;
 }
 

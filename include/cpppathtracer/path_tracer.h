@@ -189,18 +189,57 @@ private:
         std::vector<cpt_object> built, current;
         std::vector<uint64_t> updates;
     };
+    // FilterRadianceSpatial compares two records.  The camera the radiance belongs to: every
+    // call that renders into or reprojects the accumulator notes it (NoteAccumCamera).  And what the
+    // first tile's frame G-buffer holds, a camera in a scene revision: every call that writes that
+    // G-buffer notes it (NoteGBuffer) or, where it is not worth following, forgets it
+    // (gbuffer_known = false), as a new frame does.
+    struct FrameRecords {
+        bool accum_set = false, gbuffer_known = false;
+        MotionalCamera accum_cam, gbuffer_cam;
+        uint64_t gbuffer_rev = 0;
+    } records_;
+    // The DispatchRay loop's display state: SetDisplayReprojection's settings, and the previous pass
+    // of the loop, its camera copy and scene state.
+    struct DisplayLoop {
+        bool reproject = false, through_edits = false;
+        int max_history = 32;
+        float plane_tol = 1e-2f;
+        bool prev_pass = false;
+        MotionalCamera prev_cam;
+        uint64_t prev_build = 0, prev_rev = 0;
+        // through_edits: the context's captured history was captured or renewed by the loop, for the
+        // scene revision history_rev
+        bool history = false;
+        uint64_t history_rev = 0;
+    } loop_;
+    enum class CameraCopy { Advance, Query };   // GetCopy() (the renders) or a copy that leaves the sample index
     bool EnsureContext();
     bool SyncScene();
     bool SyncTile(Tile& t, const SceneSnap& snap);
     bool BindTextures(Tile& t, const std::vector<cpt_object>& objs);
     bool EnsureFrame(const MotionalCamera& cam);
+    bool Begin(const char* who, CameraCopy how, bool build, MotionalCamera& cam, std::unique_lock<std::mutex>& lk);
+    bool RequireSingleDevice(const char* who, const char* owned);
+    bool HaveFrame(const char* msg, bool and_also = true);
+    template <class Launch> bool LaunchOnTiles(const char* what, Launch launch);
+    bool GatherTiles();
     bool RenderPass(MotionalCamera& cam, int spp, bool accumulate);
-    bool DisplayPassWithHistory(MotionalCamera& cam);
     bool RenderAdaptiveTiles(MotionalCamera& cam, int min_spp, int max_spp, int batch, float rel_error, uint32_t flags,
                              int* rounds, uint64_t* passes_done);
+    bool DisplayPassWithHistory(MotionalCamera& cam);
+    bool CaptureBeforeEdit(bool had_prev, bool refreshed);
+    bool MoveDisplay(const MotionalCamera& cam, bool had_prev, bool refreshed);
+    bool PassAndMix(MotionalCamera& cam, bool join_mean);
+    bool PrevFits(bool had_prev) const;
+    bool HistoryIsPrev(cpt_ctx* ctx, bool& is_prev) const;
+    void ForgetLoopHistory() { loop_.history = false; }   // the context's history is not (or no longer) the loop's
+    void NoteAccumCamera(const MotionalCamera& cam);
+    void NoteGBuffer(const MotionalCamera& cam);
     void PipelineLoop();
     bool Fail(const char* what, cpt_ctx* ctx = nullptr);
     cpt_ctx* FrameCtx() const { return frame_ ? frame_ : (tiles_.empty() ? nullptr : tiles_[0].ctx); }
+    uint32_t WalkFlags() const { return ordered_walk_ ? CPT_TRAVERSAL_ORDERED : 0u; }
 
     std::vector<Tile> tiles_;       // one per device of the row tiling (one: the whole frame)
     cpt_ctx* frame_ = nullptr;      // row tiling: the gathered frame on the first device
@@ -212,28 +251,6 @@ private:
     int width_ = 0, height_ = 0;
     PocaTexture env_ = 0;
     std::shared_ptr<MotionalCamera> camera_;
-    // SetDisplayReprojection, and the previous pass of the loop: its camera copy and scene state
-    bool display_reproject_ = false;
-    bool display_through_edits_ = false;
-    // through_edits: the context's captured history was captured or renewed by the loop, for the
-    // scene revision loop_history_rev_
-    bool loop_history_ = false;
-    uint64_t loop_history_rev_ = 0;
-    int display_max_history_ = 32;
-    float display_plane_tol_ = 1e-2f;
-    // FilterRadianceSpatial compares two records.  The camera the radiance belongs to: every
-    // call that renders into or reprojects the accumulator notes it (NoteAccumCamera).  And what the
-    // first tile's frame G-buffer holds, a camera in a scene revision: every call that writes that
-    // G-buffer notes it (NoteGBuffer) or, where it is not worth following, forgets it
-    // (gbuffer_known_ = false), as a new frame does.
-    bool accum_cam_set_ = false, gbuffer_known_ = false;
-    MotionalCamera accum_cam_, gbuffer_cam_;
-    uint64_t gbuffer_rev_ = 0;
-    void NoteAccumCamera(const MotionalCamera& cam);
-    void NoteGBuffer(const MotionalCamera& cam);
-    bool prev_pass_ = false;
-    MotionalCamera prev_cam_;
-    uint64_t prev_scene_build_ = 0, prev_scene_rev_ = 0;
     std::vector<uint8_t> output_buffer_;   // BGRA8 handed to the callback
     bool output_pinned_ = false;           // output_buffer_ registered with cpt_host_register
     std::string err_;
