@@ -13,9 +13,11 @@ _lib = None
 # Every symbol include/cpt.h declares, with its ctypes prototype.
 _P = ctypes.c_void_p
 _I = ctypes.c_int
+_I64 = ctypes.c_int64
 _U32 = ctypes.c_uint32
 _U64 = ctypes.c_uint64
 _SZ = ctypes.c_size_t
+_F = ctypes.c_float
 PROTOTYPES = {
     "cpt_abi_version": (_I, []),
     "cpt_status_string": (ctypes.c_char_p, [_I]),
@@ -42,7 +44,7 @@ PROTOTYPES = {
     "cpt_render": (_I, [_P, _P, _I, _I, _U32]),
     "cpt_render_to_count": (_I, [_P, _P, _I, _I, _U32]),
     "cpt_topup_info": (_I, [_P, _P, _P, _P]),
-    "cpt_topup_deficit_host": (_I, [ctypes.c_float, _I, _P]),
+    "cpt_topup_deficit_host": (_I, [_F, _I, _P]),
     "cpt_synchronize": (_I, [_P]),
     "cpt_read_accum": (_I, [_P, _P]),
     "cpt_clear_accum": (_I, [_P]),
@@ -61,7 +63,7 @@ PROTOTYPES = {
     "cpt_debug_read_tile_order": (_I, [_P, _I, _P, _SZ, _P]),
     "cpt_measure_read_bandwidth": (_I, [_P, _SZ, _I, _P]),
     "cpt_measure_read_pattern": (_I, [_P, _I, _SZ, _I, _P]),
-    "cpt_cap_disk_bound": (_I, [ctypes.c_float, _P]),
+    "cpt_cap_disk_bound": (_I, [_F, _P]),
     "cpt_last_render_ms": (_I, [_P, _P]),
     "cpt_get_diag_counters": (_I, [_P, _P]),
     "cpt_get_execdiag_counters": (_I, [_P, _P]),
@@ -75,50 +77,50 @@ PROTOTYPES = {
     "cpt_reset_display": (_I, [_P]),
     "cpt_display_band": (_I, [_P, _P, _P]),
     "cpt_debug_timeline": (_I, [_P, _P, _I]),
-    "cpt_tile_costs": (_I, [_P, _P, _I, _I, ctypes.c_uint32, _P, _SZ]),
+    "cpt_tile_costs": (_I, [_P, _P, _I, _I, _U32, _P, _SZ]),
     "cpt_read_mix": (_I, [_P, _P, _SZ]),
     "cpt_math_batch": (_I, [_P, _I, _P, _P, _P, _SZ]),
     "cpt_selftest_qdiv": (_I, [_P, _I, _U64, _U64, _P, _I]),
     "cpt_set_debug_consolidation": (_I, [_P, _U32, _I, _I]),
     "cpt_set_debug_grid": (_I, [_P, _I, _I]),
-    "cpt_launch_grid_host": (_I, [_I, _I, _I, ctypes.c_int64, _I, _I, _I, _P, _P]),
-    "cpt_render_adaptive": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _U32]),
-    "cpt_adaptive_begin": (_I, [_P, _P, _I, _I, _I, ctypes.c_float, _I, _U32]),
+    "cpt_launch_grid_host": (_I, [_I, _I, _I, _I64, _I, _I, _I, _P, _P]),
+    "cpt_render_adaptive": (_I, [_P, _P, _I, _I, _I, _F, _I, _U32]),
+    "cpt_adaptive_begin": (_I, [_P, _P, _I, _I, _I, _F, _I, _U32]),
     "cpt_adaptive_step": (_I, [_P, _P]),
     "cpt_read_noise": (_I, [_P, _P, _SZ]),
     "cpt_adaptive_info": (_I, [_P, _P, _P, _I, _P]),
-    "cpt_adaptive_decide_host": (_I, [ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
+    "cpt_adaptive_decide_host": (_I, [_F, _F, _F, _F, _P, _P]),
     "cpt_read_moments": (_I, [_P, _P, _SZ]),
     "cpt_write_moments": (_I, [_P, _P, _SZ]),
-    "cpt_filter_frame": (_I, [_P, _I, ctypes.c_float, _I]),
+    "cpt_filter_frame": (_I, [_P, _I, _F, _I]),
     "cpt_read_filtered": (_I, [_P, _P, _P, _SZ]),
     "cpt_last_filter_ms": (_I, [_P, _P]),
     "cpt_filter_prepare_host": (_I, [_SZ, _P, _P, _P, _P]),
-    "cpt_filter_level_host": (_I, [_I, _I, _I, _P, _P, _P, ctypes.c_float, _I, _P]),
-    "cpt_filter_frame_spatial": (_I, [_P, _I, ctypes.c_float, _I]),
+    "cpt_filter_level_host": (_I, [_I, _I, _I, _P, _P, _P, _F, _I, _P]),
+    "cpt_filter_frame_spatial": (_I, [_P, _I, _F, _I]),
     "cpt_filter_prepare_spatial_host": (_I, [_I, _I, _P, _P, _P, _I, _P, _P]),
-    "cpt_filter_level_id_host": (_I, [_I, _I, _I, _P, _P, _P, _P, ctypes.c_float, _I, _P]),
+    "cpt_filter_level_id_host": (_I, [_I, _I, _I, _P, _P, _P, _P, _F, _I, _P]),
     "cpt_gbuffer": (_I, [_P, _P, _U32]),
     "cpt_read_gbuffer": (_I, [_P, _P, _P, _P, _P, _SZ]),
     "cpt_write_gbuffer": (_I, [_P, _P, _P, _P, _P, _SZ]),
     "cpt_trace_rays": (_I, [_P, _SZ, _P, _P, _P, _U32, _P, _P, _P]),
     "cpt_pick": (_I, [_P, _P, _I, _I, _U32, _P, _P]),
     "cpt_last_query_ms": (_I, [_P, _P]),
-    "cpt_reproject_accum": (_I, [_P, _P, _P, _I, ctypes.c_float, _U32]),
+    "cpt_reproject_accum": (_I, [_P, _P, _P, _I, _F, _U32]),
     "cpt_last_reproject_ms": (_I, [_P, _P]),
     "cpt_last_reproject_launch_ms": (_I, [_P, _P]),
-    "cpt_reproject_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_float, _P]),
+    "cpt_reproject_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P]),
     "cpt_denoise_mix_history": (_I, [_P, _P]),
     "cpt_read_display_count": (_I, [_P, _P, _SZ]),
-    "cpt_reproject_display": (_I, [_P, _P, _P, _I, ctypes.c_float, _U32]),
-    "cpt_reproject_display_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_float, _P, _P]),
+    "cpt_reproject_display": (_I, [_P, _P, _P, _I, _F, _U32]),
+    "cpt_reproject_display_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _P, _P]),
     "cpt_history_capture": (_I, [_P, _P, _U32]),
     "cpt_history_info": (_I, [_P, _P, _P]),
-    "cpt_reproject_accum_tracked": (_I, [_P, _P, _I, ctypes.c_float, _U32]),
-    "cpt_reproject_display_tracked": (_I, [_P, _P, _I, ctypes.c_float, _U32]),
+    "cpt_reproject_accum_tracked": (_I, [_P, _P, _I, _F, _U32]),
+    "cpt_reproject_display_tracked": (_I, [_P, _P, _I, _F, _U32]),
     "cpt_object_motion_host": (_I, [_P, _P, _I, _P]),
-    "cpt_reproject_tracked_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float, _P]),
-    "cpt_reproject_display_tracked_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float,
+    "cpt_reproject_tracked_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "cpt_reproject_display_tracked_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F,
                                                 _P, _P]),
 }
 
