@@ -122,6 +122,16 @@ PROTOTYPES = {
     "cpt_reproject_tracked_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "cpt_reproject_display_tracked_host": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F,
                                                 _P, _P]),
+    "cpt_set_exposure": (_I, [_P, _F]),
+    "cpt_meter_exposure": (_I, [_P, _I, _F, _I, _F]),
+    "cpt_read_exposure": (_I, [_P, _P, _P]),
+    "cpt_present": (_I, [_P, _I, _I, _F, _I, _P]),
+    "cpt_read_present": (_I, [_P, _P, _SZ]),
+    "cpt_copy_present_device": (_I, [_P, _P, _SZ, _P]),
+    "cpt_last_present_ms": (_I, [_P, _P]),
+    "cpt_present_host": (_I, [_SZ, _I, _P, _F, _I, _F, _I, _P]),
+    "cpt_meter_host": (_I, [_SZ, _I, _P, _F, _I, _F, _P, _P]),
+    "cpt_present_srgb_thresholds_host": (_I, [_P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1
@@ -137,6 +147,13 @@ CPT_SCHEDULE_CONSOLIDATE = 0x1000
 CPT_SCHEDULE_NO_CONSOLIDATE = 0x2000
 CPT_SCHEDULE_PREVIOUS = 0x4000
 CPT_TILE_ORDER_TOPUP = 4
+CPT_PRESENT_ACCUM = 0
+CPT_PRESENT_FILTERED = 1
+CPT_TONE_CLAMP = 0
+CPT_TONE_REINHARD = 1
+CPT_TONE_ACES = 2
+CPT_TRANSFER_LINEAR = 0
+CPT_TRANSFER_SRGB = 1
 CPT_ERR_INVALID_ARG = 1
 CPT_ERR_STATE = 5
 CPT_ERR_UNSUPPORTED = 6

@@ -806,6 +806,38 @@ bool PathTracer::ReprojectTracked(int max_history, float plane_tol) {
     return true;
 }
 
+// Presenting: the three calls start as every call at the current camera does and
+// need the one context that owns the accumulator and the filter planes.
+bool PathTracer::SetExposure(float exposure) {
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("SetExposure", CameraCopy::Query, true, cam, lk) || !RequireSingleDevice("SetExposure", "accumulators")) return false;
+    cpt_ctx* ctx = tiles_[0].ctx;
+    return cpt_set_exposure(ctx, exposure) == CPT_OK || Fail("cpt_set_exposure", ctx);
+}
+
+bool PathTracer::MeterExposure(bool filtered, float key, int permille, float adapt) {
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("MeterExposure", CameraCopy::Query, true, cam, lk) || !RequireSingleDevice("MeterExposure", "accumulators"))
+        return false;
+    cpt_ctx* ctx = tiles_[0].ctx;
+    return cpt_meter_exposure(ctx, filtered ? CPT_PRESENT_FILTERED : CPT_PRESENT_ACCUM, key, permille, adapt) == CPT_OK ||
+           Fail("cpt_meter_exposure", ctx);
+}
+
+bool PathTracer::Present(std::vector<uint8_t>& bgra, int tone, bool srgb, bool filtered, float white) {
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("Present", CameraCopy::Query, true, cam, lk) || !RequireSingleDevice("Present", "accumulators")) return false;
+    cpt_ctx* ctx = tiles_[0].ctx;
+    if (cpt_present(ctx, filtered ? CPT_PRESENT_FILTERED : CPT_PRESENT_ACCUM, tone, white, srgb ? CPT_TRANSFER_SRGB : CPT_TRANSFER_LINEAR,
+                    nullptr) != CPT_OK)
+        return Fail("cpt_present", ctx);
+    bgra.resize((size_t)width_ * height_ * 4);
+    return cpt_read_present(ctx, bgra.data(), bgra.size()) == CPT_OK || Fail("cpt_read_present", ctx);
+}
+
 // Counters summed over the tiles (the render flags do not ask for CPT_RENDER_STATS, so these
 // are the counters of the last counting render; GetStats after cpt-level counting renders).
 bool PathTracer::GetStats(cpt_stats* out) {

@@ -2,7 +2,7 @@
 // the accumulator / aux / RNG transfers and the counters.  The render launches, their tile
 // schedules and timing are cpt_capi_render.cpp, the adaptive render cpt_capi_adaptive.cpp, the
 // a-trous filter cpt_capi_filter.cpp, the row-tile gather cpt_capi_gather.cpp, the display path
-// cpt_capi_display.cpp, the diagnostic probes and self-tests cpt_capi_probes.cpp.  The scene half
+// cpt_capi_display.cpp, presenting cpt_capi_present.cpp, the diagnostic probes and self-tests cpt_capi_probes.cpp.  The scene half
 // (upload, material slots, walk trees, device refit) is cpt_scene.cpp; the host BVH builds and the XORWOW tables are cpt_host_bvh.cpp /
 // cpt_host_rng.cpp.
 #include <hip/hip_runtime.h>
@@ -154,7 +154,7 @@ int cpt_create(int device, cpt_ctx** out) {
     if (e == hipSuccess) e = c->own_stream.create(hipStreamNonBlocking);
     for (DevEvent* ev : {&c->t_render.t0, &c->t_render.t1, &c->ev_main, &c->t_display.t0, &c->t_display.t1, &c->t_filter.t0,
                           &c->t_filter.t1, &c->t_query.t0, &c->t_query.t1, &c->t_reproject.t0, &c->t_reproject.t1,
-                          &c->ev_reproject[0], &c->ev_reproject[1]})
+                          &c->ev_reproject[0], &c->ev_reproject[1], &c->t_present.t0, &c->t_present.t1})
         if (e == hipSuccess) e = ev->create();
     for (DevEvent* ev : {&c->ev_ready, &c->ev_gathered, &c->ev_caller, &c->ev_copied, &c->ev_round, &c->ev_switch})
         if (e == hipSuccess) e = ev->create(hipEventDisableTiming);

@@ -4,8 +4,8 @@
 // render), cpt_capi_filter.cpp (a-trous filter), cpt_capi_gather.cpp (row-tile gather),
 // cpt_capi_display.cpp (display path), cpt_capi_query.cpp (G-buffer, ray queries, picking),
 // cpt_capi_reproject.cpp (reprojection to a moved camera), cpt_capi_topup.cpp (top-up render),
-// cpt_capi_probes.cpp (diagnostic probes, self-tests) and
-// cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  Host code only.
+// cpt_capi_probes.cpp (diagnostic probes, self-tests), cpt_capi_present.cpp (presenting, DESIGN.md
+// §26) and cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -182,6 +182,14 @@ struct TopupState {
     bool planned = false;       // a cpt_render_to_count has been queued since cpt_set_frame
 };
 
+// Presenting (cpt_capi_present.cpp; allocated on the frame's first cpt_set_exposure,
+// cpt_meter_exposure, cpt_read_exposure or cpt_present).
+struct PresentState {
+    DevBuf<uint8_t> d_bgra;     // the last cpt_present's BGRA8 plane ([npix][4])
+    DevBuf<uint32_t> d_words;   // the meter's 257 histogram words, then the exposure's bits (1.0f at first)
+    bool presented = false;     // a cpt_present has been queued since cpt_set_frame
+};
+
 struct Frame {
     bool set = false, rng_set = false;
     DevBuf<int32_t> d_rows;
@@ -198,6 +206,7 @@ struct Frame {
     GBufferState gbuffer;
     ReprojectState reproject;
     TopupState topup;
+    PresentState present;
 };
 
 // A pair of timing events around a subsystem's last launches, once they have been recorded.
@@ -223,6 +232,7 @@ struct cpt_ctx {
     TimedSpan t_reproject; // the last cpt_reproject_accum's or cpt_reproject_display's launches ...
     DevEvent ev_reproject[2];   // ... and the two points between them: after each G-buffer trace
     bool reproject_tracked = false;   // ... of a tracked call: the trace at `from` did not run
+    TimedSpan t_present;   // the last cpt_meter_exposure's or cpt_present's launches
     std::string err;
 
     // scene

@@ -285,4 +285,14 @@ hipError_t launch_denoise_mix(const float4* accum, const float* normal, const fl
 // `value` into the first w_eff columns of `rows` rows of a count plane of `width` columns
 hipError_t launch_fill_count(float* count, int width, int w_eff, int rows, float value, hipStream_t stream);
 
+// Presenting (cpt_present.hip).  `src`: the accumulator or a filter plane, npix
+// float4; `words`: the 257 histogram words, then the exposure's bits.  launch_meter zeroes the
+// histogram on the stream, fills it (at most `cus` x 4 workgroups) and resolves it into the
+// exposure with a second, one-workgroup launch.  launch_present reads the exposure and writes bgra
+// ([npix][4] bytes, 16-byte aligned).
+hipError_t launch_meter(const float4* src, size_t npix, int source, float key, int permille, float adapt, uint32_t* words,
+                        int cus, hipStream_t stream);
+hipError_t launch_present(const float4* src, size_t npix, int source, int tone, float white, int transfer,
+                          const uint32_t* words, uint8_t* bgra, hipStream_t stream);
+
 }  // namespace cpt

@@ -7,6 +7,14 @@
 //                [--objects N] [--animate K [--animate-step X]] [--pick X,Y] [--orbit N [--reproject]]
 //                [--orbit N [--animate K] --display-reproject on|off|edits --bgra frame.bin]
 //                [--animate K --reproject] [--fill T] [--filter-spatial [LEVELS] [--look-aside]]
+//                [--present clamp|reinhard|aces [--exposure auto|X] [--linear] --bgra frame.bin]
+//
+// --present CURVE (with plain --spp, and with --orbit N --reproject [--fill T] [--filter-spatial]; not
+// with --display-reproject or --dispatch, whose loop has its own 8-bit output): the last frame, the
+// filtered one with --filter-spatial, is presented through the exposure, the tone curve and the sRGB
+// transfer (PathTracer::Present; --linear: the reference's 255.99 * linear bytes) and
+// --bgra gets the BGRA8 frame.  --exposure auto meters the frame first (PathTracer::MeterExposure: the
+// median luminance to 0.18), --exposure X sets it; without either it is 1.
 //
 // --filter-spatial [LEVELS] (without --adaptive: with plain --spp, and with --orbit N --reproject
 // [--fill T]): the last frame is filtered without moments, its variance estimated from each pixel's
@@ -196,6 +204,8 @@ int main(int argc, char** argv) {
     float animate_step = 0.75f;
     bool reproject = false;
     std::string display_reproject;   // "", "on" or "off"
+    std::string present, exposure;   // --present clamp|reinhard|aces, --exposure auto|X
+    bool present_linear = false;     // --linear: CPT_TRANSFER_LINEAR
     for (int i = 1; i < argc; i += 2) {
         std::string k = argv[i];
         if (k == "--filter") {
@@ -217,6 +227,11 @@ int main(int argc, char** argv) {
         }
         if (k == "--reproject") {
             reproject = true;
+            --i;
+            continue;
+        }
+        if (k == "--linear") {
+            present_linear = true;
             --i;
             continue;
         }
@@ -242,6 +257,8 @@ int main(int argc, char** argv) {
         else if (k == "--orbit") orbit = std::stoi(v);
         else if (k == "--fill") fill = std::stoi(v);
         else if (k == "--display-reproject") display_reproject = v;
+        else if (k == "--present") present = v;
+        else if (k == "--exposure") exposure = v;
         else if (k == "--adaptive") adaptive = std::stof(v);
         else if (k == "--min-spp") min_spp = std::stoi(v);
         else if (k == "--batch") batch = std::stoi(v);
@@ -320,6 +337,18 @@ int main(int argc, char** argv) {
     if (look_aside && filter_spatial < 0) {
         fprintf(stderr, "--look-aside wants --filter-spatial\n");
         return 2;
+    }
+    int present_tone = -1;
+    float present_exposure = 0.f;   // --exposure X (0: auto or none)
+    if (!present.empty() || !exposure.empty() || present_linear) {
+        present_tone = present == "clamp" ? CPT_TONE_CLAMP : present == "reinhard" ? CPT_TONE_REINHARD : present == "aces" ? CPT_TONE_ACES : -1;
+        if (!exposure.empty() && exposure != "auto") present_exposure = std::stof(exposure);
+        if (present_tone < 0 || !display_reproject.empty() || dispatch > 0 || adaptive >= 0.f || animate > 0 || (orbit > 0 && !reproject) ||
+            bgra_out.empty() || (!exposure.empty() && exposure != "auto" && !(present_exposure > 0.f))) {
+            fprintf(stderr, "--present wants clamp, reinhard or aces, --bgra, [--exposure auto|X > 0] [--linear], and plain --spp or "
+                            "--orbit N --reproject [--fill T] [--filter-spatial]; not --display-reproject, --dispatch, --adaptive or --animate\n");
+            return 2;
+        }
     }
     if (!display_reproject.empty()) {
         if (orbit <= 0 || (display_reproject != "on" && display_reproject != "off" && display_reproject != "edits")) {
@@ -471,6 +500,16 @@ int main(int argc, char** argv) {
             if (!tracer.FilterRadianceSpatial(filter_spatial)) { fprintf(stderr, "FilterRadianceSpatial: %s\n", tracer.LastError().c_str()); return 1; }
             printf("looked aside (G-buffer at the turned camera) and filtered again\n");
         }
+    }
+    if (present_tone >= 0) {
+        const bool from_filtered = filter_spatial >= 0;
+        if (exposure == "auto" && !tracer.MeterExposure(from_filtered)) { fprintf(stderr, "MeterExposure: %s\n", tracer.LastError().c_str()); return 1; }
+        if (present_exposure > 0.f && !tracer.SetExposure(present_exposure)) { fprintf(stderr, "SetExposure: %s\n", tracer.LastError().c_str()); return 1; }
+        std::vector<uint8_t> frame;
+        if (!tracer.Present(frame, present_tone, !present_linear, from_filtered)) { fprintf(stderr, "Present: %s\n", tracer.LastError().c_str()); return 1; }
+        std::ofstream f(bgra_out, std::ios::binary);
+        f.write(reinterpret_cast<const char*>(frame.data()), (std::streamsize)frame.size());
+        printf("presented: %s, %s, exposure %s\n", present.c_str(), present_linear ? "linear" : "sRGB", exposure.empty() ? "1" : exposure.c_str());
     }
     const bool filtered = filter_spatial >= 0 || (adaptive >= 0.f && filter_levels >= 0 && animate == 0);
     if (!pfm.empty() && !(filtered ? tracer.SaveFilteredPFM(pfm) : tracer.SaveRadiancePFM(pfm))) { fprintf(stderr, "%s\n", tracer.LastError().c_str()); return 1; }

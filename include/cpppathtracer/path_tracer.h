@@ -12,8 +12,8 @@
 //   SetMaxRecursionDepth, SetSeed, SetDevice, SetDevices (row tiling over several GPUs),
 //   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance, FilterRadianceSpatial,
 //   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
-//   Reproject, CaptureHistory, ReprojectTracked, RenderToCount, SetDisplayReprojection, GetStats,
-//   Stop.
+//   Reproject, CaptureHistory, ReprojectTracked, RenderToCount, SetDisplayReprojection, SetExposure,
+//   MeterExposure, Present, GetStats, Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -165,6 +165,19 @@ public:
     // gathers, as Render does.
     bool RenderToCount(int target);
     bool ReprojectTracked(int max_history = 32, float plane_tol = 1e-2f);
+    // Presenting the HDR frame (cpt_set_exposure, cpt_meter_exposure, cpt_present; an
+    // addition: the DispatchRay loop clamps its own running mean to [0, 1]).  Present: the radiance
+    // accumulator, or with `filtered` the last FilterRadiance / FilterRadianceSpatial result, times
+    // the exposure, through the tone curve (CPT_TONE_CLAMP, CPT_TONE_REINHARD with `white` > 0,
+    // CPT_TONE_ACES) and the sRGB transfer (`srgb` false: the reference's 255.99 * linear) into
+    // BGRA8[width*height*4].  MeterExposure moves the exposure towards key / (the permille-th
+    // thousandth of the frame's positive luminances, to an eighth of an octave) by the share `adapt`
+    // in [0, 1]; SetExposure sets it (finite, > 0; 1 on a new frame).  The radiance, the RNG, the
+    // filter result and the display loop's state are left as they are.  Not available with
+    // SetDevices(n > 1) (false, LastError).
+    bool SetExposure(float exposure);
+    bool MeterExposure(bool filtered = false, float key = 0.18f, int permille = 500, float adapt = 1.0f);
+    bool Present(std::vector<uint8_t>& bgra, int tone = CPT_TONE_ACES, bool srgb = true, bool filtered = false, float white = 4.0f);
     bool GetStats(cpt_stats* out);
     void Stop();                                 // stop the render thread (also in ~PathTracer)
     const std::string& LastError() const { return err_; }

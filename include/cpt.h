@@ -798,6 +798,70 @@ int cpt_last_display_ms(cpt_ctx* ctx, float* ms);
  * uninitialised; here both are zeroed when the frame is created and by this call). */
 int cpt_reset_display(cpt_ctx* ctx);
 
+/* Presenting an HDR frame (an addition; the reference's only 8-bit output is the
+ * display loop above, which owns its running mean, clamps to [0, 1] and writes 255.99 * linear):
+ * the accumulator of any frame, or the last filter result, to BGRA8 through an exposure, a tone
+ * curve and a transfer, and an exposure meter.  All of it is f32 + - * / in a stated order,
+ * comparisons, integer operations and one table (cpt_present.hpp), so the device, the host hooks
+ * below and a numpy restatement agree byte for byte.
+ *   source colour c: CPT_PRESENT_ACCUM: n = accum.w; c = accum.xyz / n where n > 0 and finite,
+ *     else c = 0 and the pixel is unsourced.  CPT_PRESENT_FILTERED: the rgb cpt_read_filtered reads.
+ *   c' = c > 0 ? c : 0 (NaN, negatives, -0 become +0);  x = min(c' * e, 65504), e the exposure.
+ *   y = CPT_TONE_CLAMP: min(x, 1);  CPT_TONE_REINHARD: min((x (1 + x / (w w))) / (1 + x), 1), w =
+ *     `white`;  CPT_TONE_ACES: min(max((x (2.51 x + 0.03)) / (x (2.43 x + 0.59) + 0.14), 0), 1).
+ *   byte = CPT_TRANSFER_LINEAR: (uint8_t)(255.99f * y), the reference's;  CPT_TRANSFER_SRGB: the
+ *     number of k in 1..255 with T[k] <= y, T[k] the smallest float t with 255 oetf(t) >= k - 0.5.
+ *   4 bytes per pixel: B, G, R, 255.
+ * The exposure is a word in device memory (1 after cpt_set_frame), so a meter and a present queue
+ * behind each other with no host round trip.  The meter: a pixel is metered if it is sourced and
+ * l = luma(c') is finite and > 0; it adds one to word clamp((int)(bits(l) >> 20) - 888, 0, 255) of a
+ * histogram (eight bins per octave from 2^-16 to 2^16), every other pixel to word 256.  With N the
+ * sum of words 0..255: N == 0 leaves e; otherwise rank = min(N permille / 1000, N - 1), b the least
+ * bin whose cumulative count exceeds rank, L the float with bits (b + 888) << 20, target = key / L,
+ * and e <- target when adapt == 1, else e + (target - e) adapt.
+ * All calls need a frame (any rows; CPT_ERR_STATE without one, while an adaptive render is pending,
+ * and for CPT_PRESENT_FILTERED without a filter result), write only the present state (the BGRA
+ * plane, the histogram, the exposure) and nothing at all when they fail; no allocation after the
+ * frame's first of them. */
+#define CPT_PRESENT_ACCUM    0
+#define CPT_PRESENT_FILTERED 1
+#define CPT_TONE_CLAMP    0
+#define CPT_TONE_REINHARD 1
+#define CPT_TONE_ACES     2
+#define CPT_TRANSFER_LINEAR 0
+#define CPT_TRANSFER_SRGB   1
+/* Sets the exposure (finite, > 0; else CPT_ERR_INVALID_ARG), on the context's stream. */
+int cpt_set_exposure(cpt_ctx* ctx, float exposure);
+/* Meters `source` and moves the exposure, asynchronously on the context's stream.  key finite and
+ * > 0, permille 0..1000, adapt in [0, 1]; else CPT_ERR_INVALID_ARG. */
+int cpt_meter_exposure(cpt_ctx* ctx, int source, float key, int permille, float adapt);
+/* The exposure and the last meter's 257 histogram words (zeros before the first); waits for the
+ * stream.  Either pointer may be NULL. */
+int cpt_read_exposure(cpt_ctx* ctx, float* exposure, uint32_t* hist257);
+/* Presents `source` into the context's BGRA8 plane ([n_rows*width][4]), asynchronously.  white is
+ * read by CPT_TONE_REINHARD only but must be > 0 and not NaN.  bgra_host, when not NULL, receives a
+ * copy that follows the kernel on the stream (the kernel never writes host memory): wait with
+ * cpt_synchronize before reading it. */
+int cpt_present(cpt_ctx* ctx, int source, int tone, float white, int transfer, uint8_t* bgra_host);
+/* The last cpt_present's plane: read back (capacity in bytes, at least n_rows*width*4; waits), or
+ * copied on the device, ordered against caller_stream as cpt_copy_accum_device.  CPT_ERR_STATE
+ * before the frame's first cpt_present. */
+int cpt_read_present(cpt_ctx* ctx, uint8_t* bgra, size_t capacity);
+int cpt_copy_present_device(cpt_ctx* ctx, void* device_dst, size_t bytes, void* caller_stream);
+/* Device time of the last cpt_meter_exposure's or cpt_present's launches, whichever was later (HIP
+ * events on the context's stream); waits for it. */
+int cpt_last_present_ms(cpt_ctx* ctx, float* ms);
+/* HOST ONLY, no GPU: the functions the kernels run.  `src`: [npix][4] floats, the accumulator, for
+ * CPT_PRESENT_ACCUM; [npix][3], the filtered rgb, for CPT_PRESENT_FILTERED.  cpt_present_host writes
+ * bgra [npix][4].  cpt_meter_host writes hist257 (may be NULL) and moves *exposure.
+ * cpt_present_srgb_thresholds_host: the table, t256[0] = 0 and T[1..255].  Arguments as the device
+ * calls'; CPT_ERR_INVALID_ARG likewise. */
+int cpt_present_host(size_t npix, int source, const float* src, float exposure, int tone, float white, int transfer,
+                     uint8_t* bgra);
+int cpt_meter_host(size_t npix, int source, const float* src, float key, int permille, float adapt, float* exposure,
+                   uint32_t* hist257);
+int cpt_present_srgb_thresholds_host(float* t256);
+
 /* HBM streaming-read ceiling of the device (the roofline peak, measured on
  * the box): `iters` grid-stride 16-B-per-lane read passes over a fresh `bytes`-byte buffer
  * (use >> 256 MiB so the Infinity Cache cannot serve it), GB/s from HIP events. */
