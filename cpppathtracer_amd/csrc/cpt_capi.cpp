@@ -2,9 +2,11 @@
 // the accumulator / aux / RNG transfers and the counters.  The render launches, their tile
 // schedules and timing are cpt_capi_render.cpp, the adaptive render cpt_capi_adaptive.cpp, the
 // a-trous filter cpt_capi_filter.cpp, the row-tile gather cpt_capi_gather.cpp, the display path
-// cpt_capi_display.cpp, presenting cpt_capi_present.cpp, the diagnostic probes and self-tests cpt_capi_probes.cpp.  The scene half
-// (upload, material slots, walk trees, device refit) is cpt_scene.cpp; the host BVH builds and the XORWOW tables are cpt_host_bvh.cpp /
-// cpt_host_rng.cpp.
+// cpt_capi_display.cpp, the first-hit queries cpt_capi_query.cpp, the reprojection
+// cpt_capi_reproject.cpp, the top-up render cpt_capi_topup.cpp, presenting cpt_capi_present.cpp,
+// the diagnostic probes and self-tests cpt_capi_probes.cpp.  The scene half (upload, material
+// slots, walk trees, device refit) is cpt_scene.cpp; the host BVH builds and the XORWOW tables are
+// cpt_host_bvh.cpp / cpt_host_rng.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -85,8 +87,7 @@ int check_device_error(cpt_ctx* c) {
 
 // Drain the context's stream, then report a device-side error of the work it ran.
 int sync_checked(cpt_ctx* c) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    if (int rc = drain(c)) return rc;
     return check_device_error(c);
 }
 
@@ -152,9 +153,9 @@ int cpt_create(int device, cpt_ctx** out) {
     if (e == hipSuccess) e = hipDeviceGetAttribute(&c->grid.cus, hipDeviceAttributeMultiprocessorCount, device);
     c->grid.cus = std::max(c->grid.cus, 1);
     if (e == hipSuccess) e = c->own_stream.create(hipStreamNonBlocking);
-    for (DevEvent* ev : {&c->t_render.t0, &c->t_render.t1, &c->ev_main, &c->t_display.t0, &c->t_display.t1, &c->t_filter.t0,
-                          &c->t_filter.t1, &c->t_query.t0, &c->t_query.t1, &c->t_reproject.t0, &c->t_reproject.t1,
-                          &c->ev_reproject[0], &c->ev_reproject[1], &c->t_present.t0, &c->t_present.t1})
+    for (TimedSpan* t : {&c->t_render, &c->t_display, &c->t_filter, &c->t_query, &c->t_reproject, &c->t_present})
+        if (e == hipSuccess) e = t->create();
+    for (DevEvent* ev : {&c->ev_main, &c->ev_reproject[0], &c->ev_reproject[1]})   // the points inside two of the spans
         if (e == hipSuccess) e = ev->create();
     for (DevEvent* ev : {&c->ev_ready, &c->ev_gathered, &c->ev_caller, &c->ev_copied, &c->ev_round, &c->ev_switch})
         if (e == hipSuccess) e = ev->create(hipEventDisableTiming);
@@ -256,8 +257,7 @@ int cpt_set_frame(cpt_ctx* c, int width, int height, const int32_t* rows, int n_
         r.resize(height);
         for (int y = 0; y < height; ++y) r[y] = y;
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    if (int rc = drain(c)) return rc;
     // releases everything the previous frame held; with it goes the captured history of the tracked
     // reprojection (ReprojectState: planes of the old size, the motion table and its events)
     c->frame = Frame{};
@@ -270,10 +270,9 @@ int cpt_set_frame(cpt_ctx* c, int width, int height, const int32_t* rows, int n_
     c->rows_h = r;
     const size_t npix = c->npix();
     if (c->n_rows > 0) {
-        int rc;
-        if ((rc = f.d_rows.ensure(c, r.size())) != CPT_OK) return rc;
-        HIP_TRY(c, hipMemcpy(f.d_rows, r.data(), r.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        if ((rc = f.d_rng.ensure(c, 6 * npix)) != CPT_OK || (rc = f.d_accum.ensure(c, npix)) != CPT_OK) return rc;
+        if (int rc = f.d_rows.ensure(c, r.size())) return rc;
+        if (int rc = write_in(c, f.d_rows, r.data(), r.size())) return rc;
+        if (int rc = ensure_all(c, f.d_rng, 6 * npix, f.d_accum, npix)) return rc;
         // on the context's stream, and waited for: a device hipMemset returns before the fill has
         // run and is ordered on the null stream only, which the context's non-blocking stream does
         // not wait for; on a busy GPU the fill could land after cpt_init_rng's kernel or a render
@@ -291,9 +290,7 @@ int cpt_init_rng(cpt_ctx* c, uint64_t seed) {
     if (!f.set) return fail(c, CPT_ERR_STATE, "cpt_init_rng: cpt_set_frame first");
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->n_rows == 0) { f.rng_set = true; return CPT_OK; }
-    int rc;
-    if ((rc = f.d_scratch_w.ensure(c, 5 * (size_t)c->width)) != CPT_OK) return rc;
-    if ((rc = f.d_scratch_m.ensure(c, (size_t)c->n_rows * 800)) != CPT_OK) return rc;
+    if (int rc = ensure_all(c, f.d_scratch_w, 5 * (size_t)c->width, f.d_scratch_m, (size_t)c->n_rows * 800)) return rc;
     f.schedule.rng_replaced();
     uint32_t st[6];
     curand_seed_state(seed, st);
@@ -311,18 +308,14 @@ int cpt_read_rng(cpt_ctx* c, uint32_t* planar6) {
     if (!c || !planar6) return CPT_ERR_INVALID_ARG;
     if (!c->frame.set) return fail(c, CPT_ERR_STATE, "cpt_read_rng: no frame");
     if (int rc = sync_checked(c)) return rc;
-    size_t n = 6 * c->npix();
-    if (n) HIP_TRY(c, hipMemcpy(planar6, c->frame.d_rng, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return CPT_OK;
+    return read_back(c, planar6, c->frame.d_rng, 6 * c->npix());
 }
 
 int cpt_write_rng(cpt_ctx* c, const uint32_t* planar6) {
     if (!c || !planar6) return CPT_ERR_INVALID_ARG;
     if (!c->frame.set) return fail(c, CPT_ERR_STATE, "cpt_write_rng: no frame");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
-    size_t n = 6 * c->npix();
-    if (n) HIP_TRY(c, hipMemcpy(c->frame.d_rng, planar6, n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = drain(c)) return rc;
+    if (int rc = write_in(c, c->frame.d_rng, planar6, 6 * c->npix())) return rc;
     c->frame.rng_set = true;
     c->frame.schedule.draws_moved();
     return CPT_OK;
@@ -337,9 +330,7 @@ int cpt_read_accum(cpt_ctx* c, float* rgba) {
     if (!c || !rgba) return CPT_ERR_INVALID_ARG;
     if (!c->frame.set) return fail(c, CPT_ERR_STATE, "cpt_read_accum: no frame");
     if (int rc = sync_checked(c)) return rc;
-    size_t n = c->npix();
-    if (n) HIP_TRY(c, hipMemcpy(rgba, c->frame.d_accum, n * sizeof(float4), hipMemcpyDeviceToHost));
-    return CPT_OK;
+    return read_back(c, rgba, c->frame.d_accum, c->npix());
 }
 
 int cpt_clear_accum(cpt_ctx* c) {
@@ -354,12 +345,11 @@ int cpt_clear_accum(cpt_ctx* c) {
 int cpt_read_aux(cpt_ctx* c, float* normal3, float* depth) {
     if (!c) return CPT_ERR_INVALID_ARG;
     if (!c->frame.d_normal || !c->frame.d_depth) return fail(c, CPT_ERR_STATE, "cpt_read_aux: render with CPT_RENDER_AUX first");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
-    size_t n = c->npix();
-    if (normal3 && n) HIP_TRY(c, hipMemcpy(normal3, c->frame.d_normal, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (depth && n) HIP_TRY(c, hipMemcpy(depth, c->frame.d_depth, n * sizeof(float), hipMemcpyDeviceToHost));
-    return CPT_OK;
+    if (int rc = drain(c)) return rc;
+    const size_t n = c->npix();
+    if (normal3)
+        if (int rc = read_back(c, normal3, c->frame.d_normal, 3 * n)) return rc;
+    return depth ? read_back(c, depth, c->frame.d_depth, n) : CPT_OK;
 }
 
 // Checkpoint / resume: the accumulator and the first-hit aux buffers restored
@@ -367,26 +357,19 @@ int cpt_read_aux(cpt_ctx* c, float* normal3, float* depth) {
 int cpt_write_accum(cpt_ctx* c, const float* rgba) {
     if (!c || !rgba) return CPT_ERR_INVALID_ARG;
     if (!c->frame.set) return fail(c, CPT_ERR_STATE, "cpt_write_accum: no frame");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
-    const size_t n = c->npix();
-    if (n) HIP_TRY(c, hipMemcpy(c->frame.d_accum, rgba, n * sizeof(float4), hipMemcpyHostToDevice));
-    return CPT_OK;
+    if (int rc = drain(c)) return rc;
+    return write_in(c, c->frame.d_accum, rgba, c->npix());
 }
 
 int cpt_write_aux(cpt_ctx* c, const float* normal3, const float* depth) {
     if (!c || !normal3 || !depth) return CPT_ERR_INVALID_ARG;
-    if (!c->frame.set) return fail(c, CPT_ERR_STATE, "cpt_write_aux: no frame");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    Frame& f = c->frame;
+    if (!f.set) return fail(c, CPT_ERR_STATE, "cpt_write_aux: no frame");
+    if (int rc = drain(c)) return rc;
     const size_t n = c->npix();
-    int rc;
-    if ((rc = c->frame.d_normal.ensure(c, n * 3)) != CPT_OK || (rc = c->frame.d_depth.ensure(c, n)) != CPT_OK) return rc;
-    if (n) {
-        HIP_TRY(c, hipMemcpy(c->frame.d_normal, normal3, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(c->frame.d_depth, depth, n * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return CPT_OK;
+    if (int rc = f.ensure_aux(c, n)) return rc;
+    if (int rc = write_in(c, f.d_normal, normal3, 3 * n)) return rc;
+    return write_in(c, f.d_depth, depth, n);
 }
 
 int cpt_copy_accum_device(cpt_ctx* c, void* dst, size_t bytes, void* caller_stream) {
@@ -399,10 +382,8 @@ int cpt_copy_accum_device(cpt_ctx* c, void* dst, size_t bytes, void* caller_stre
 // `count` of the context's 64-bit counters from `first` on, once its stream has drained.
 static int read_counters(cpt_ctx* c, void* out, int first, int count) {
     if (!c || !out) return CPT_ERR_INVALID_ARG;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
-    HIP_TRY(c, hipMemcpy(out, c->d_stats + first, count * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return CPT_OK;
+    if (int rc = drain(c)) return rc;
+    return read_back(c, out, c->d_stats, (size_t)count, (size_t)first);
 }
 
 int cpt_get_stats(cpt_ctx* c, cpt_stats* out) {

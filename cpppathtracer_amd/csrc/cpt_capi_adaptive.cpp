@@ -61,7 +61,7 @@ int enqueue_round(cpt_ctx* c) {
 int adaptive_begin(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, int batch, float rel_error, int max_depth,
                    uint32_t flags, const char* who) {
     if (!c || !cam) return CPT_ERR_INVALID_ARG;
-    if (max_depth < 0 || max_depth > (int)cpt::MAX_RECURSION_DEPTH_SET)
+    if (!max_depth_ok(max_depth))
         return fail(c, CPT_ERR_INVALID_ARG, "%s: max_depth %d (must be 0..32)", who, max_depth);
     if (batch < 1 || min_spp < batch || max_spp < min_spp || min_spp % batch || max_spp % batch ||
         (min_spp < 2 * batch && min_spp != max_spp))
@@ -96,13 +96,10 @@ int adaptive_begin(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, 
     int rc;
     a.aux = (flags & CPT_RENDER_AUX) != 0;
     a.stats = (flags & CPT_RENDER_STATS) != 0;
-    if (a.aux) {
-        if ((rc = f.d_normal.ensure(c, npix * 3)) != CPT_OK) return rc;
-        if ((rc = f.d_depth.ensure(c, npix)) != CPT_OK) return rc;
-    }
-    if ((rc = f.adaptive.d_snap.ensure(c, npix)) != CPT_OK || (rc = f.adaptive.d_stat.ensure(c, 4 * npix)) != CPT_OK ||
-        (rc = f.adaptive.d_keep.ensure(c, tiles)) != CPT_OK || (rc = f.adaptive.d_order[0].ensure(c, tiles)) != CPT_OK ||
-        (rc = f.adaptive.d_order[1].ensure(c, tiles)) != CPT_OK || (rc = f.adaptive.d_count.ensure(c, 2)) != CPT_OK)
+    if (a.aux && (rc = f.ensure_aux(c, npix)) != CPT_OK) return rc;
+    AdaptiveState& ad = f.adaptive;
+    if ((rc = ensure_all(c, ad.d_snap, npix, ad.d_stat, 4 * npix, ad.d_keep, tiles, ad.d_order[0], tiles, ad.d_order[1], tiles,
+                         ad.d_count, 2)) != CPT_OK)
         return rc;
     // a new estimate: no batch seen; the snapshot is the accumulator the first round adds to
     HIP_TRY(c, hipMemsetAsync(f.adaptive.d_stat, 0, 4 * npix * sizeof(float), s));
@@ -113,7 +110,7 @@ int adaptive_begin(cpt_ctx* c, const cpt_camera* cam, int min_spp, int max_spp, 
 
     fill_params(c, cam, batch, max_depth, flags, a.p);
     c->t_render.recorded = false;   // ev_start .. ev_stop span the rounds: no timing until the last step
-    HIP_TRY(c, hipEventRecord(c->t_render.t0, s));
+    if ((rc = c->t_render.begin(c, s)) != CPT_OK) return rc;
     if (flags & CPT_SCHEDULE_COST) {
         // one pilot, sized for the whole render; the rounds filter its order
         if ((rc = cost_pilot(c, a.p, cost_pilot_passes(max_spp), s)) != CPT_OK) return rc;
@@ -159,10 +156,9 @@ int adaptive_step(cpt_ctx* c, int* active_tiles, const char* who) {
         return CPT_OK;
     }
     if (a.round > 0) {   // rounds ran (a context without rows has none, and no timing)
-        HIP_TRY(c, hipEventRecord(c->t_render.t1, s));
+        if (int rc = c->t_render.end(c, s)) return rc;
         HIP_TRY(c, hipStreamSynchronize(s));
         c->last_launches = (int)f.adaptive.rounds.size();
-        c->t_render.recorded = true;
         f.schedule.draws_moved();
     }
     f.adaptive.pending = AdaptiveState::Pending{};
@@ -213,8 +209,7 @@ int cpt_read_noise(cpt_ctx* c, float* rel, size_t capacity) {
     const size_t n = c->npix();
     if (capacity < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_noise: %zu < %zu pixels", capacity, n);
     if (int rc = sync_checked(c)) return rc;
-    if (n) HIP_TRY(c, hipMemcpy(rel, c->frame.adaptive.d_stat + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost));
-    return CPT_OK;
+    return read_back(c, rel, c->frame.adaptive.d_stat, n, 3 * n);   // the fourth plane
 }
 
 int cpt_adaptive_info(cpt_ctx* c, int* rounds, uint32_t* active_tiles_per_round, int capacity, uint64_t* passes_done) {

@@ -42,9 +42,7 @@ static int denoise_band(cpt_ctx* c, uint32_t cur_sample_idx, int y0, int y1, uin
         const size_t n = cap_rows * c->width;
         DevBuf<float> mix, count;
         DevBuf<uint8_t> bgra;
-        int rc;
-        if ((rc = mix.ensure(c, n * 3)) != CPT_OK || (rc = count.ensure(c, n)) != CPT_OK || (rc = bgra.ensure(c, n * 4)) != CPT_OK)
-            return rc;
+        if (int rc = ensure_all(c, mix, n * 3, count, n, bgra, n * 4)) return rc;
         HIP_TRY(c, hipMemsetAsync(mix, 0, n * 3 * sizeof(float), s));
         HIP_TRY(c, hipMemsetAsync(count, 0, n * sizeof(float), s));
         HIP_TRY(c, hipMemsetAsync(bgra, 0, n * 4, s));
@@ -73,12 +71,11 @@ static int denoise_band(cpt_ctx* c, uint32_t cur_sample_idx, int y0, int y1, uin
     if (int rc = f.display.d_sink.ensure(c, cpt::DN_SINK_SLOTS)) return rc;
     if (history)
         if (int rc = f.display.fill_count(c)) return rc;
-    HIP_TRY(c, hipEventRecord(c->t_display.t0, s));
+    if (int rc = c->t_display.begin(c, s)) return rc;
     HIP_TRY(c, cpt::launch_denoise_mix(f.d_accum, f.d_normal, f.d_depth, f.display.d_mix, history ? f.display.d_count.get() : nullptr,
                                       f.display.d_bgra, host_alias, f.display.d_sink, c->width, c->height, row0, c->n_rows, y0, y1,
                                       cur_sample_idx, c->grid, s));
-    HIP_TRY(c, hipEventRecord(c->t_display.t1, s));
-    c->t_display.recorded = true;
+    if (int rc = c->t_display.end(c, s)) return rc;
     if (!history) {
         // every pixel of the launch region now has, by definition, cur_sample_idx samples
         f.display.last_idx = cur_sample_idx;

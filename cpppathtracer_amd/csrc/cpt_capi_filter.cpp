@@ -42,14 +42,11 @@ int filter_frame(cpt_ctx* c, const char* who, bool spatial, int levels, float si
     }
     HIP_TRY(c, hipSetDevice(c->device));
     FilterState& ft = f.filter;
-    int rc;
-    if ((rc = ft.d_plane[0].ensure(c, npix)) != CPT_OK || (rc = ft.d_plane[1].ensure(c, npix)) != CPT_OK ||
-        (rc = ft.d_ok.ensure(c, npix)) != CPT_OK)
-        return rc;
+    if (int rc = ensure_all(c, ft.d_plane[0], npix, ft.d_plane[1], npix, ft.d_ok, npix)) return rc;
     ft.result = -1;
     hipStream_t s = c->stream();
     const float sigma2 = sigma_l * sigma_l;
-    HIP_TRY(c, hipEventRecord(c->t_filter.t0, s));
+    if (int rc = c->t_filter.begin(c, s)) return rc;
     if (spatial)
         HIP_TRY(c, cpt::launch_filter_prepare_spatial(f.d_accum, g.d_id, g.d_normal, c->width, c->height, normal_sharpness_log2,
                                                       ft.d_plane[0], ft.d_ok, s));
@@ -63,8 +60,7 @@ int filter_frame(cpt_ctx* c, const char* who, bool spatial, int levels, float si
             HIP_TRY(c, cpt::launch_filter_level(ft.d_plane[l & 1], f.d_normal, ft.d_ok, ft.d_plane[(l + 1) & 1], c->width, c->height,
                                                1 << l, sigma2, normal_sharpness_log2, s));
     }
-    HIP_TRY(c, hipEventRecord(c->t_filter.t1, s));
-    c->t_filter.recorded = true;
+    if (int rc = c->t_filter.end(c, s)) return rc;
     ft.result = levels & 1;
     return CPT_OK;
 }
@@ -89,7 +85,7 @@ int cpt_read_filtered(cpt_ctx* c, float* rgb, float* variance, size_t capacity_p
     if (capacity_pixels < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_filtered: %zu < %zu pixels", capacity_pixels, n);
     if (int rc = sync_checked(c)) return rc;
     std::vector<float> plane(4 * n);
-    HIP_TRY(c, hipMemcpy(plane.data(), f.filter.d_plane[f.filter.result], n * sizeof(float4), hipMemcpyDeviceToHost));
+    if (int rc = read_back(c, plane.data(), f.filter.d_plane[f.filter.result], n)) return rc;
     for (size_t i = 0; i < n; ++i) {
         if (rgb) {
             rgb[3 * i] = plane[4 * i];
@@ -112,8 +108,7 @@ int cpt_read_moments(cpt_ctx* c, float* planar4, size_t capacity) {
     const size_t n = 4 * c->npix();
     if (capacity < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_moments: %zu < %zu floats", capacity, n);
     if (int rc = sync_checked(c)) return rc;
-    if (n) HIP_TRY(c, hipMemcpy(planar4, f.adaptive.d_stat, n * sizeof(float), hipMemcpyDeviceToHost));
-    return CPT_OK;
+    return read_back(c, planar4, f.adaptive.d_stat, n);
 }
 
 int cpt_write_moments(cpt_ctx* c, const float* planar4, size_t count) {
@@ -122,10 +117,9 @@ int cpt_write_moments(cpt_ctx* c, const float* planar4, size_t count) {
     if (!f.set) return fail(c, CPT_ERR_STATE, "cpt_write_moments: no frame");
     const size_t n = 4 * c->npix();
     if (count < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_write_moments: %zu < %zu floats", count, n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    if (int rc = drain(c)) return rc;
     if (int rc = f.adaptive.d_stat.ensure(c, n)) return rc;
-    if (n) HIP_TRY(c, hipMemcpy(f.adaptive.d_stat, planar4, n * sizeof(float), hipMemcpyHostToDevice));
+    if (int rc = write_in(c, f.adaptive.d_stat, planar4, n)) return rc;
     f.adaptive.adopt_result();
     return CPT_OK;
 }

@@ -80,9 +80,7 @@ int cpt_gather_rows(cpt_ctx* dst, cpt_ctx* src) {
         // waits for the device, the blocking copy below does not wait for dst's stream)
         gm->d_map.reset();
         if (int rc = gm->d_map.ensure(dst, map.size())) return rc;
-        if (!map.empty()) {
-            HIP_TRY(dst, hipMemcpy(gm->d_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        if (int rc = write_in(dst, gm->d_map, map.data(), map.size())) return rc;
         gm->src_gen = src->frame_gen;
         gm->dst_gen = dst->frame_gen;
         gm->src_device = src->device;

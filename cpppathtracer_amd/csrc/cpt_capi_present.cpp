@@ -91,11 +91,9 @@ int cpt_meter_exposure(cpt_ctx* c, int source, float key, int permille, float ad
     if (int rc = require_source(c, "cpt_meter_exposure", source, &src)) return rc;
     if (int rc = ensure_state(c)) return rc;
     hipStream_t s = c->stream();
-    HIP_TRY(c, hipEventRecord(c->t_present.t0, s));
+    if (int rc = c->t_present.begin(c, s)) return rc;
     HIP_TRY(c, cpt::launch_meter(src, c->npix(), source, key, permille, adapt, c->frame.present.d_words, c->grid.cus, s));
-    HIP_TRY(c, hipEventRecord(c->t_present.t1, s));
-    c->t_present.recorded = true;
-    return CPT_OK;
+    return c->t_present.end(c, s);
 }
 
 int cpt_read_exposure(cpt_ctx* c, float* exposure, uint32_t* hist257) {
@@ -104,7 +102,7 @@ int cpt_read_exposure(cpt_ctx* c, float* exposure, uint32_t* hist257) {
     if (int rc = ensure_state(c)) return rc;
     if (int rc = sync_checked(c)) return rc;
     uint32_t words[prs::HIST_WORDS + 1];
-    HIP_TRY(c, hipMemcpy(words, c->frame.present.d_words, sizeof(words), hipMemcpyDeviceToHost));
+    if (int rc = read_back(c, words, c->frame.present.d_words, prs::HIST_WORDS + 1)) return rc;
     if (exposure) *exposure = prs::float_of(words[EXPOSURE_WORD]);
     if (hist257) std::memcpy(hist257, words, prs::HIST_WORDS * sizeof(uint32_t));
     return CPT_OK;
@@ -121,10 +119,9 @@ int cpt_present(cpt_ctx* c, int source, int tone, float white, int transfer, uin
     PresentState& p = c->frame.present;
     hipStream_t s = c->stream();
     const size_t npix = c->npix();
-    HIP_TRY(c, hipEventRecord(c->t_present.t0, s));
+    if (int rc = c->t_present.begin(c, s)) return rc;
     HIP_TRY(c, cpt::launch_present(src, npix, source, tone, white, transfer, p.d_words, p.d_bgra, s));
-    HIP_TRY(c, hipEventRecord(c->t_present.t1, s));
-    c->t_present.recorded = true;
+    if (int rc = c->t_present.end(c, s)) return rc;
     p.presented = true;
     if (bgra_host && npix) HIP_TRY(c, hipMemcpyAsync(bgra_host, p.d_bgra, npix * 4, hipMemcpyDeviceToHost, s));
     return CPT_OK;
@@ -137,8 +134,7 @@ int cpt_read_present(cpt_ctx* c, uint8_t* bgra, size_t capacity) {
     const size_t bytes = c->npix() * 4;
     if (capacity < bytes) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_present: %zu < %zu bytes", capacity, bytes);
     if (int rc = sync_checked(c)) return rc;
-    if (bytes) HIP_TRY(c, hipMemcpy(bgra, f.present.d_bgra, bytes, hipMemcpyDeviceToHost));
-    return CPT_OK;
+    return read_back(c, bgra, f.present.d_bgra, bytes);
 }
 
 int cpt_copy_present_device(cpt_ctx* c, void* device_dst, size_t bytes, void* caller_stream) {

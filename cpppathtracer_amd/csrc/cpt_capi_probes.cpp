@@ -48,8 +48,7 @@ int cpt_debug_read_nodes(cpt_ctx* c, void* out, size_t capacity_bytes, size_t* n
     if (capacity_bytes < bytes)
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_debug_read_nodes: %zu < %zu bytes", capacity_bytes, bytes);
     if (int rc = sync_checked(c)) return rc;
-    HIP_TRY(c, hipMemcpy(out, c->d_nodes, bytes, hipMemcpyDeviceToHost));
-    return CPT_OK;
+    return read_back(c, out, c->d_nodes, c->lin.size());
 }
 
 int cpt_debug_read_tile_order(cpt_ctx* c, int which, uint32_t* out, size_t capacity, size_t* n) {
@@ -72,7 +71,7 @@ int cpt_debug_read_tile_order(cpt_ctx* c, int which, uint32_t* out, size_t capac
         src = f.topup.d_order;
         uint32_t active = 0;
         if (int rc = sync_checked(c)) return rc;
-        HIP_TRY(c, hipMemcpy(&active, f.topup.d_words, sizeof(active), hipMemcpyDeviceToHost));
+        if (int rc = read_back(c, &active, f.topup.d_words, 1)) return rc;
         if (active > len) return fail(c, CPT_ERR_DEVICE, "cpt_debug_read_tile_order: %u of %zu tiles active", active, len);
         len = active;
     } else {
@@ -96,14 +95,11 @@ int cpt_math_batch(cpt_ctx* c, int op,const float* a, const float* b, float* out
     HIP_TRY(c, hipSetDevice(c->device));
     DevBuf<float> da, db, dout;
     int rc;
-    if ((rc = da.ensure(c, n)) != CPT_OK || (rc = db.ensure(c, n)) != CPT_OK || (rc = dout.ensure(c, n)) != CPT_OK)
-        return rc;
-    HIP_TRY(c, hipMemcpy(da, a, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(db, b, n * 4, hipMemcpyHostToDevice));
+    if ((rc = ensure_all(c, da, n, db, n, dout, n)) != CPT_OK) return rc;
+    if ((rc = write_in(c, da, a, n)) != CPT_OK || (rc = write_in(c, db, b, n)) != CPT_OK) return rc;
     HIP_TRY(c, cpt::launch_math_batch(op, da, db, dout, n, c->stream()));
     HIP_TRY(c, hipStreamSynchronize(c->stream()));
-    HIP_TRY(c, hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
-    return CPT_OK;
+    return read_back(c, out, dout, n);
 }
 
 int cpt_cap_disk_bound(float radius, float* out) {
@@ -118,8 +114,7 @@ int cpt_measure_read_bandwidth(cpt_ctx* c, size_t bytes, int iters, float* gbps)
     const size_t n = bytes / 16;
     DevBuf<float4> d;
     DevBuf<float> o;
-    int rc;
-    if ((rc = d.ensure(c, n)) != CPT_OK || (rc = o.ensure(c, 1)) != CPT_OK) return rc;
+    if (int rc = ensure_all(c, d, n, o, 1)) return rc;
     HIP_TRY(c, hipMemsetAsync(d, 0, n * 16, c->stream()));
     const int grid = 8 * c->grid.cus;   // 8 blocks of 256 lanes per CU, grid-stride
     return timed_reads(c, true, iters, (double)n * 16.0, gbps,
@@ -133,8 +128,7 @@ int cpt_measure_read_pattern(cpt_ctx* c, int bytes_per_lane, size_t bytes, int i
     const size_t n_lanes = bytes / (size_t)bytes_per_lane;
     DevBuf<uint8_t> d;
     DevBuf<float> o;
-    int rc;
-    if ((rc = d.ensure(c, n_lanes * bytes_per_lane)) != CPT_OK || (rc = o.ensure(c, 1)) != CPT_OK) return rc;
+    if (int rc = ensure_all(c, d, n_lanes * bytes_per_lane, o, 1)) return rc;
     HIP_TRY(c, hipMemsetAsync(d, 0, n_lanes * bytes_per_lane, c->stream()));
     const float* lanes = reinterpret_cast<const float*>(d.get());
     const int grid = 8 * c->grid.cus;
@@ -150,8 +144,7 @@ int cpt_selftest_qdiv(cpt_ctx* c, int which, uint64_t n, uint64_t seed, uint64_t
     HIP_TRY(c, hipMemsetAsync(d, 0, out_len * sizeof(unsigned long long), c->stream()));
     HIP_TRY(c, cpt::launch_selftest_qdiv(which, n, seed, d, out_len, c->stream()));
     HIP_TRY(c, hipStreamSynchronize(c->stream()));
-    HIP_TRY(c, hipMemcpy(out, d, out_len * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return CPT_OK;
+    return read_back(c, out, d, (size_t)out_len);
 }
 
 }  // extern "C"

@@ -14,7 +14,6 @@ using namespace cpt::ctx;
 
 namespace {
 
-constexpr uint32_t WALK_FLAGS = CPT_TRAVERSAL_ORDERED | CPT_TRAVERSAL_PLAIN_LEAVES;
 constexpr size_t MAX_RAYS = (size_t)1 << 30;   // the kernel's 32-bit lane index, with room
 
 // The kernel parameters of a query: the scene, the walk of `flags`, the frame's rows, and `cam`
@@ -29,7 +28,7 @@ void query_params(cpt_ctx* c, const cpt_camera* cam, uint32_t flags, cpt::KParam
 // What cpt_gbuffer and cpt_pick ask before they launch: walk flags only, a scene, a frame, a
 // camera of the frame's size.
 int pixel_query_ok(cpt_ctx* c, const cpt_camera* cam, uint32_t flags, const char* who) {
-    if (flags & ~WALK_FLAGS) return fail(c, CPT_ERR_INVALID_ARG, "%s: flags 0x%x (only CPT_TRAVERSAL_* bits)", who, flags);
+    if (int rc = walk_flags_only(c, who, flags)) return rc;
     if (!c->scene_set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_scene first", who);
     if (!c->frame.set) return fail(c, CPT_ERR_STATE, "%s: cpt_set_frame first", who);
     if (cam->width != c->width || cam->height != c->height)
@@ -40,11 +39,9 @@ int pixel_query_ok(cpt_ctx* c, const cpt_camera* cam, uint32_t flags, const char
 // One launch of the query kernel between the timing events.
 int timed_query(cpt_ctx* c, const cpt::KParams& p, const cpt::QueryRays* rays, cpt::QueryPixels px, const cpt::QueryOut& out) {
     hipStream_t s = c->stream();
-    HIP_TRY(c, hipEventRecord(c->t_query.t0, s));
+    if (int rc = c->t_query.begin(c, s)) return rc;
     HIP_TRY(c, cpt::launch_ray_query(p, c->d_rank_obj, rays, px, out, s));
-    HIP_TRY(c, hipEventRecord(c->t_query.t1, s));
-    c->t_query.recorded = true;
-    return CPT_OK;
+    return c->t_query.end(c, s);
 }
 
 }  // namespace
@@ -59,15 +56,11 @@ int cpt_gbuffer(cpt_ctx* c, const cpt_camera* cam, uint32_t flags) {
         return fail(c, CPT_ERR_UNSUPPORTED, "cpt_gbuffer: frame of %zu 8x8 tiles (max %u)", cpt::ctx::n_tiles(c), UINT32_MAX / 64);
     HIP_TRY(c, hipSetDevice(c->device));
     GBufferState& g = c->frame.gbuffer;
-    const size_t npix = c->npix();
-    int rc;
-    if ((rc = g.d_id.ensure(c, npix)) != CPT_OK || (rc = g.d_t.ensure(c, npix)) != CPT_OK ||
-        (rc = g.d_normal.ensure(c, 3 * npix)) != CPT_OK || (rc = g.d_albedo.ensure(c, 3 * npix)) != CPT_OK)
-        return rc;
+    if (int rc = g.ensure(c, c->npix())) return rc;
     cpt::KParams p;
     query_params(c, cam, flags, p);
     const cpt::QueryOut out{g.d_id, g.d_t, g.d_normal, g.d_albedo};
-    if ((rc = timed_query(c, p, nullptr, cpt::QueryPixels{-1, -1}, out)) != CPT_OK) return rc;
+    if (int rc = timed_query(c, p, nullptr, cpt::QueryPixels{-1, -1}, out)) return rc;
     g.valid = true;
     return CPT_OK;
 }
@@ -79,12 +72,12 @@ int cpt_read_gbuffer(cpt_ctx* c, int32_t* id, float* t, float* normal3, float* a
     const size_t n = c->npix();
     if (capacity_pixels < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_read_gbuffer: %zu < %zu pixels", capacity_pixels, n);
     if (int rc = sync_checked(c)) return rc;
-    if (n == 0) return CPT_OK;
-    if (id) HIP_TRY(c, hipMemcpy(id, g.d_id, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (t) HIP_TRY(c, hipMemcpy(t, g.d_t, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (normal3) HIP_TRY(c, hipMemcpy(normal3, g.d_normal, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    if (albedo3) HIP_TRY(c, hipMemcpy(albedo3, g.d_albedo, 3 * n * sizeof(float), hipMemcpyDeviceToHost));
-    return CPT_OK;
+    int rc = CPT_OK;
+    if (id) rc = read_back(c, id, g.d_id, n);
+    if (t && rc == CPT_OK) rc = read_back(c, t, g.d_t, n);
+    if (normal3 && rc == CPT_OK) rc = read_back(c, normal3, g.d_normal, 3 * n);
+    if (albedo3 && rc == CPT_OK) rc = read_back(c, albedo3, g.d_albedo, 3 * n);
+    return rc;
 }
 
 int cpt_write_gbuffer(cpt_ctx* c, const int32_t* id, const float* t, const float* normal3, const float* albedo3,
@@ -93,26 +86,22 @@ int cpt_write_gbuffer(cpt_ctx* c, const int32_t* id, const float* t, const float
     if (!c->frame.set) return fail(c, CPT_ERR_STATE, "cpt_write_gbuffer: no frame");
     const size_t n = c->npix();
     if (count_pixels < n) return fail(c, CPT_ERR_INVALID_ARG, "cpt_write_gbuffer: %zu < %zu pixels", count_pixels, n);
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    if (int rc = drain(c)) return rc;
     GBufferState& g = c->frame.gbuffer;
-    // a plane that was never written starts as zeros: one that is new here, or all four when no
-    // G-buffer is valid yet
-    const bool fresh[4] = {!g.valid || g.d_id.capacity() < n, !g.valid || g.d_t.capacity() < n,
-                           !g.valid || g.d_normal.capacity() < 3 * n, !g.valid || g.d_albedo.capacity() < 3 * n};
-    int rc;
-    if ((rc = g.d_id.ensure(c, n)) != CPT_OK || (rc = g.d_t.ensure(c, n)) != CPT_OK ||
-        (rc = g.d_normal.ensure(c, 3 * n)) != CPT_OK || (rc = g.d_albedo.ensure(c, 3 * n)) != CPT_OK)
-        return rc;
+    const size_t had[4] = {g.d_id.capacity(), g.d_t.capacity(), g.d_normal.capacity(), g.d_albedo.capacity()};
+    if (int rc = g.ensure(c, n)) return rc;
+    // one row per plane: the caller's array, the device plane, its 4-byte elements per pixel
+    const struct { const void* host; void* dev; size_t per_pixel; } planes[4] = {
+        {id, g.d_id.get(), 1}, {t, g.d_t.get(), 1}, {normal3, g.d_normal.get(), 3}, {albedo3, g.d_albedo.get(), 3}};
     if (n) {
-        if (id) HIP_TRY(c, hipMemcpy(g.d_id, id, n * sizeof(int32_t), hipMemcpyHostToDevice));
-        else if (fresh[0]) HIP_TRY(c, hipMemsetAsync(g.d_id, 0, n * sizeof(int32_t), c->stream()));
-        if (t) HIP_TRY(c, hipMemcpy(g.d_t, t, n * sizeof(float), hipMemcpyHostToDevice));
-        else if (fresh[1]) HIP_TRY(c, hipMemsetAsync(g.d_t, 0, n * sizeof(float), c->stream()));
-        if (normal3) HIP_TRY(c, hipMemcpy(g.d_normal, normal3, 3 * n * sizeof(float), hipMemcpyHostToDevice));
-        else if (fresh[2]) HIP_TRY(c, hipMemsetAsync(g.d_normal, 0, 3 * n * sizeof(float), c->stream()));
-        if (albedo3) HIP_TRY(c, hipMemcpy(g.d_albedo, albedo3, 3 * n * sizeof(float), hipMemcpyHostToDevice));
-        else if (fresh[3]) HIP_TRY(c, hipMemsetAsync(g.d_albedo, 0, 3 * n * sizeof(float), c->stream()));
+        for (int k = 0; k < 4; ++k) {
+            const size_t count = planes[k].per_pixel * n;
+            // a plane that was never written starts as zeros: one that is new here (by its capacity
+            // before the ensure), or all four when no G-buffer is valid yet
+            const bool fresh = !g.valid || had[k] < count;
+            if (planes[k].host) HIP_TRY(c, hipMemcpy(planes[k].dev, planes[k].host, count * 4, hipMemcpyHostToDevice));
+            else if (fresh) HIP_TRY(c, hipMemsetAsync(planes[k].dev, 0, count * 4, c->stream()));
+        }
         HIP_TRY(c, hipStreamSynchronize(c->stream()));   // the fills: a later copy into the plane must not race them
     }
     g.valid = true;
@@ -122,7 +111,7 @@ int cpt_write_gbuffer(cpt_ctx* c, const int32_t* id, const float* t, const float
 int cpt_trace_rays(cpt_ctx* c, size_t n, const float* origin3, const float* dir3, const float* tmin, uint32_t flags,
                    int32_t* id, float* t, float* normal3) {
     if (!c) return CPT_ERR_INVALID_ARG;
-    if (flags & ~WALK_FLAGS) return fail(c, CPT_ERR_INVALID_ARG, "cpt_trace_rays: flags 0x%x (only CPT_TRAVERSAL_* bits)", flags);
+    if (int rc = walk_flags_only(c, "cpt_trace_rays", flags)) return rc;
     if (n > MAX_RAYS) return fail(c, CPT_ERR_INVALID_ARG, "cpt_trace_rays: %zu rays (max %zu)", n, MAX_RAYS);
     if (n > 0 && (!origin3 || !dir3 || !id || !t || !normal3))
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_trace_rays: origin3, dir3, id, t and normal3 must not be NULL");
@@ -130,10 +119,7 @@ int cpt_trace_rays(cpt_ctx* c, size_t n, const float* origin3, const float* dir3
     if (n == 0) return CPT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     // all device memory before the first copy: nothing is allocated between the launch and the read-back
-    int rc;
-    if ((rc = c->d_query_rays.ensure(c, 7 * n)) != CPT_OK || (rc = c->d_query_out.ensure(c, 4 * n)) != CPT_OK ||
-        (rc = c->d_query_id.ensure(c, n)) != CPT_OK)
-        return rc;
+    if (int rc = ensure_all(c, c->d_query_rays, 7 * n, c->d_query_out, 4 * n, c->d_query_id, n)) return rc;
     hipStream_t s = c->stream();
     float* const d_o = c->d_query_rays;
     float* const d_d = d_o + 3 * n;
@@ -147,7 +133,7 @@ int cpt_trace_rays(cpt_ctx* c, size_t n, const float* origin3, const float* dir3
     query_params(c, nullptr, flags, p);
     const cpt::QueryRays rays{d_o, d_d, tmin ? d_tmin : nullptr, (uint32_t)n};
     const cpt::QueryOut out{c->d_query_id, d_t, d_n, nullptr};
-    if ((rc = timed_query(c, p, &rays, cpt::QueryPixels{-1, -1}, out)) != CPT_OK) return rc;
+    if (int rc = timed_query(c, p, &rays, cpt::QueryPixels{-1, -1}, out)) return rc;
     HIP_TRY(c, hipMemcpyAsync(id, c->d_query_id, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(t, d_t, n * sizeof(float), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(normal3, d_n, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -161,19 +147,18 @@ int cpt_pick(cpt_ctx* c, const cpt_camera* cam, int x, int y, uint32_t flags, in
     if (x < 0 || x >= c->width || y < 0 || y >= c->height)
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_pick: pixel (%d, %d) outside the %dx%d frame", x, y, c->width, c->height);
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = c->d_query_out.ensure(c, 4)) != CPT_OK || (rc = c->d_query_id.ensure(c, 1)) != CPT_OK) return rc;
+    if (int rc = ensure_all(c, c->d_query_out, 4, c->d_query_id, 1)) return rc;
     cpt::KParams p;
     query_params(c, cam, flags, p);
     float* const d_t = c->d_query_out;
     const cpt::QueryOut out{c->d_query_id, d_t, d_t + 1, nullptr};
-    if ((rc = timed_query(c, p, nullptr, cpt::QueryPixels{x, y}, out)) != CPT_OK) return rc;
+    if (int rc = timed_query(c, p, nullptr, cpt::QueryPixels{x, y}, out)) return rc;
     hipStream_t s = c->stream();
     int32_t h_id = -1;
     float h_t = 0.f;
     HIP_TRY(c, hipMemcpyAsync(&h_id, c->d_query_id, sizeof(h_id), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(&h_t, d_t, sizeof(h_t), hipMemcpyDeviceToHost, s));
-    if ((rc = sync_checked(c)) != CPT_OK) return rc;
+    if (int rc = sync_checked(c)) return rc;
     *object = h_id;
     if (t) *t = h_t;
     return CPT_OK;

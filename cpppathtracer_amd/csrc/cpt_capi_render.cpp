@@ -145,9 +145,7 @@ int TileSchedule::previous_begin(cpt_ctx* c, cpt::KParams& p, hipStream_t s) {
 // renders (the RNG's d word counts them all), and the order, a heuristic, costs ~65 us to rebuild.
 int TileSchedule::previous_refresh(cpt_ctx* c, const cpt::KParams& p, hipStream_t s) {
     if (prev_order_valid && ++prev_since_order < PREV_ORDER_EVERY) return CPT_OK;
-    int rc;
-    if ((rc = d_scratch.ensure(c, cpt::tile_schedule_scratch_bytes(c->width, c->n_rows))) != CPT_OK) return rc;
-    if ((rc = d_prev_order.ensure(c, n_tiles(c))) != CPT_OK) return rc;
+    if (int rc = ensure_all(c, d_scratch, cpt::tile_schedule_scratch_bytes(c->width, c->n_rows), d_prev_order, n_tiles(c))) return rc;
     HIP_TRY(c, cpt::launch_tile_order_from_draws(p, d_prev_d, d_scratch, d_scratch.capacity(), d_prev_order, s));
     prev_d_valid = true;
     prev_order_valid = true;
@@ -164,9 +162,9 @@ constexpr int PILOT_MAX = 16, PILOT_DIV = 128;
 int cpt::ctx::cost_pilot_passes(int spp) { return std::min(PILOT_MAX, std::max(1, spp / PILOT_DIV)); }
 int cpt::ctx::cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStream_t s) {
     Frame& f = c->frame;
-    int rc;
-    if ((rc = f.schedule.d_scratch.ensure(c, cpt::tile_schedule_scratch_bytes(c->width, c->n_rows))) != CPT_OK) return rc;
-    if ((rc = f.schedule.d_cost_order.ensure(c, n_tiles(c))) != CPT_OK) return rc;
+    if (int rc = ensure_all(c, f.schedule.d_scratch, cpt::tile_schedule_scratch_bytes(c->width, c->n_rows),
+                            f.schedule.d_cost_order, n_tiles(c)))
+        return rc;
     HIP_TRY(c, cpt::launch_tile_schedule(p, passes, f.schedule.d_scratch, f.schedule.d_scratch.capacity(), f.schedule.d_cost_order,
                                          c->grid, s));
     return CPT_OK;
@@ -202,7 +200,7 @@ extern "C" {
 
 int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32_t flags) {
     if (!c || !cam) return CPT_ERR_INVALID_ARG;
-    if (spp < 0 || max_depth < 0 || max_depth > (int)cpt::MAX_RECURSION_DEPTH_SET)
+    if (spp < 0 || !max_depth_ok(max_depth))
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_render: spp %d, max_depth %d (must be 0..32)", spp, max_depth);
     CPT_REFUSE_PENDING(c, "cpt_render");
     if (int rc = renderable(c, cam, "cpt_render")) return rc;
@@ -211,23 +209,20 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
     hipStream_t s = c->stream();
     int rc;
     const bool aux = (flags & CPT_RENDER_AUX) != 0;
-    if (aux) {
-        if ((rc = f.d_normal.ensure(c, c->npix() * 3)) != CPT_OK) return rc;
-        if ((rc = f.d_depth.ensure(c, c->npix())) != CPT_OK) return rc;
-    }
+    if (aux && (rc = f.ensure_aux(c, c->npix())) != CPT_OK) return rc;
     cpt::KParams p;
     fill_params(c, cam, spp, max_depth, flags, p);
     const bool wavefront = (flags & CPT_PATH_WAVEFRONT) != 0;
     const bool work = spp > 0 && c->n_rows > 0;
     if (wavefront && (rc = ensure_wavefront(c, p, s)) != CPT_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->t_render.t0, s));
+    if ((rc = c->t_render.begin(c, s)) != CPT_OK) return rc;
     if (wavefront) {
         if (!p.accumulate && c->n_rows > 0) HIP_TRY(c, hipMemsetAsync(f.d_accum, 0, c->npix() * sizeof(float4), s));
         int launches = 0;
         HIP_TRY(c, hipEventRecord(c->ev_main, s));
         HIP_TRY(c, cpt::launch_wavefront(p, f.wavefront.view, (flags & CPT_RENDER_STATS) != 0, aux, c->grid, s, &launches));
         c->last_launches = launches;
-        HIP_TRY(c, hipEventRecord(c->t_render.t1, s));
+        if ((rc = c->t_render.end(c, s)) != CPT_OK) return rc;
     } else {
         c->last_launches = 1;
         const bool cost = (flags & CPT_SCHEDULE_COST) && work;
@@ -240,10 +235,9 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
         if ((rc = consolidation_slab(c, p, spp, flags)) != CPT_OK) return rc;
         HIP_TRY(c, hipEventRecord(c->ev_main, s));
         HIP_TRY(c, cpt::launch_megakernel(p, (flags & CPT_RENDER_STATS) != 0, aux, c->grid, s));
-        HIP_TRY(c, hipEventRecord(c->t_render.t1, s));
+        if ((rc = c->t_render.end(c, s)) != CPT_OK) return rc;
         if (previous && (rc = f.schedule.previous_refresh(c, p, s)) != CPT_OK) return rc;
     }
-    c->t_render.recorded = true;
     if (flags & CPT_RENDER_SYNC) return sync_checked(c);
     return CPT_OK;
 }
@@ -254,15 +248,14 @@ int cpt_render(cpt_ctx* c, const cpt_camera* cam, int spp, int max_depth, uint32
 // maximum over its pixels, not their sum (cpt_megakernel.hip, the tile_cost update).
 int cpt_tile_costs(cpt_ctx* c, const cpt_camera* cam, int passes, int max_depth, uint32_t flags, uint32_t* out,
                    size_t n_out) {
-    if (!c || !cam || !out || passes < 1 || max_depth < 0 || max_depth > (int)cpt::MAX_RECURSION_DEPTH_SET)
-        return CPT_ERR_INVALID_ARG;
+    if (!c || !cam || !out || passes < 1 || !max_depth_ok(max_depth)) return CPT_ERR_INVALID_ARG;
     if (int rc = renderable(c, cam, "cpt_tile_costs")) return rc;
     if (n_out < n_tiles(c)) return fail(c, CPT_ERR_INVALID_ARG, "cpt_tile_costs: %zu < %zu tiles", n_out, n_tiles(c));
     if (n_tiles(c) == 0) return CPT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream();
     cpt::KParams p;
-    fill_params(c, cam, passes, max_depth, flags & (CPT_TRAVERSAL_ORDERED | CPT_TRAVERSAL_PLAIN_LEAVES), p);
+    fill_params(c, cam, passes, max_depth, flags & WALK_FLAGS, p);
     if (int rc = cost_pilot(c, p, passes, s)) return rc;
     // the unsorted costs are the scratch's first n_tiles words (the sort writes elsewhere)
     HIP_TRY(c, hipMemcpyAsync(out, c->frame.schedule.d_scratch, n_tiles(c) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));

@@ -21,15 +21,13 @@ namespace rp = cpt::reproject;
 
 namespace {
 
-constexpr uint32_t WALK_FLAGS = CPT_TRAVERSAL_ORDERED | CPT_TRAVERSAL_PLAIN_LEAVES;
-
 bool args_ok(int max_history, float plane_tol) { return max_history >= 1 && rp::finite(plane_tol) && plane_tol >= 0.f; }
 
 // What every device call here (`who`) asks before it writes anything.
 int checked(cpt_ctx* c, const char* who, const cpt_camera* from, const cpt_camera* to, int max_history, float plane_tol,
             uint32_t flags) {
     if (!from || !to) return fail(c, CPT_ERR_INVALID_ARG, "%s: a camera is NULL", who);
-    if (flags & ~WALK_FLAGS) return fail(c, CPT_ERR_INVALID_ARG, "%s: flags 0x%x (only CPT_TRAVERSAL_* bits)", who, flags);
+    if (int rc = walk_flags_only(c, who, flags)) return rc;
     if (!args_ok(max_history, plane_tol))
         return fail(c, CPT_ERR_INVALID_ARG, "%s: max_history %d (>= 1), plane_tol %g (finite, >= 0)", who, max_history,
                     (double)plane_tol);
@@ -46,15 +44,10 @@ int checked(cpt_ctx* c, const char* who, const cpt_camera* from, const cpt_camer
 
 // The planes every call traces into: the frame's G-buffer and the history's id and distance.
 int ensure_planes(cpt_ctx* c) {
-    GBufferState& g = c->frame.gbuffer;
     ReprojectState& r = c->frame.reproject;
     const size_t npix = c->npix();
-    int rc;
-    if ((rc = g.d_id.ensure(c, npix)) != CPT_OK || (rc = g.d_t.ensure(c, npix)) != CPT_OK ||
-        (rc = g.d_normal.ensure(c, 3 * npix)) != CPT_OK || (rc = g.d_albedo.ensure(c, 3 * npix)) != CPT_OK ||
-        (rc = r.d_id.ensure(c, npix)) != CPT_OK || (rc = r.d_t.ensure(c, npix)) != CPT_OK)
-        return rc;
-    return CPT_OK;
+    if (int rc = c->frame.gbuffer.ensure(c, npix)) return rc;
+    return ensure_all(c, r.d_id, npix, r.d_t, npix);
 }
 
 // The whole G-buffer at p's camera into the frame's own planes (the kernel writes all four).
@@ -75,7 +68,7 @@ int trace(cpt_ctx* c, const cpt::KParams* p0, const cpt::KParams& p1, hipStream_
     ReprojectState& r = c->frame.reproject;
     // the trace at `from` overwrites the planes a captured history lives in: it is gone
     if (p0) r.captured = false;
-    HIP_TRY(c, hipEventRecord(c->t_reproject.t0, s));
+    if (int rc = c->t_reproject.begin(c, s)) return rc;
     if (p0)
         HIP_TRY(c, cpt::launch_ray_query(*p0, c->d_rank_obj, nullptr, cpt::QueryPixels{-1, -1},
                                          cpt::QueryOut{r.d_id, r.d_t, g.d_normal, nullptr}, s));
@@ -89,11 +82,8 @@ int trace(cpt_ctx* c, const cpt::KParams* p0, const cpt::KParams& p1, hipStream_
 int tracked_ready(cpt_ctx* c, const char* who) {
     ReprojectState& r = c->frame.reproject;
     if (!r.captured) return fail(c, CPT_ERR_STATE, "%s: no captured history (cpt_history_capture first)", who);
-    int rc;
-    if ((rc = ensure_planes(c)) != CPT_OK || (rc = r.d_id_next.ensure(c, c->npix())) != CPT_OK ||
-        (rc = r.d_t_next.ensure(c, c->npix())) != CPT_OK)
-        return rc;
-    return CPT_OK;
+    if (int rc = ensure_planes(c)) return rc;
+    return ensure_all(c, r.d_id_next, c->npix(), r.d_t_next, c->npix());
 }
 
 // The motion table of the objects since the capture, uploaded on the stream; *table stays nullptr
@@ -159,11 +149,7 @@ int reproject(cpt_ctx* c, const char* who, const cpt_camera* from, const cpt_cam
     const size_t npix = c->npix();
     int rc;
     if ((rc = TRACKED ? tracked_ready(c, who) : ensure_planes(c)) != CPT_OK) return rc;
-    if (DISPLAY) {
-        if ((rc = d.d_mix_next.ensure(c, 3 * npix)) != CPT_OK || (rc = d.d_count_next.ensure(c, npix)) != CPT_OK) return rc;
-    } else if ((rc = r.d_accum.ensure(c, npix)) != CPT_OK) {
-        return rc;
-    }
+    if ((rc = DISPLAY ? ensure_all(c, d.d_mix_next, 3 * npix, d.d_count_next, npix) : r.d_accum.ensure(c, npix)) != CPT_OK) return rc;
     if (TRACKED) from = &r.cam;
     cpt::KParams p0, p1;
     fill_params(c, from, 0, 0, flags, p0);
@@ -205,8 +191,7 @@ int reproject(cpt_ctx* c, const char* who, const cpt_camera* from, const cpt_cam
     }
     if ((rc = trace(c, TRACKED ? nullptr : &p0, p1, s)) != CPT_OK) return rc;
     HIP_TRY(c, cpt::launch_reproject(args, s));
-    HIP_TRY(c, hipEventRecord(c->t_reproject.t1, s));
-    c->t_reproject.recorded = true;
+    if ((rc = c->t_reproject.end(c, s)) != CPT_OK) return rc;
     c->reproject_tracked = TRACKED;
     // the second planes are the accumulator, or the display state, from here on: work already queued
     // holds the old pointers by value and runs before the kernel; every later call reads the members.

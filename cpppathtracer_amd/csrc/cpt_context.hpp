@@ -5,7 +5,10 @@
 // cpt_capi_display.cpp (display path), cpt_capi_query.cpp (G-buffer, ray queries, picking),
 // cpt_capi_reproject.cpp (reprojection to a moved camera), cpt_capi_topup.cpp (top-up render),
 // cpt_capi_probes.cpp (diagnostic probes, self-tests), cpt_capi_present.cpp (presenting, DESIGN.md
-// §26) and cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  Host code only.
+// §26) and cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  What those files
+// would otherwise each spell out is here once: the timed spans (TimedSpan), the buffer lists
+// (GBufferState::ensure, Frame::ensure_aux; ensure_all, read_back and write_in are cpt_devmem.hpp's),
+// the two drains, and the argument checks more than one file makes.  Host code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -147,6 +150,9 @@ struct GBufferState {
     DevBuf<float> d_t;                  // hit distance
     DevBuf<float> d_normal, d_albedo;   // [npix][3] each
     bool valid = false;                 // a cpt_gbuffer has been queued, or a cpt_write_gbuffer made, since cpt_set_frame
+
+    // the four planes of `npix` pixels
+    int ensure(cpt_ctx* c, size_t npix) { return cpt::ctx::ensure_all(c, d_id, npix, d_t, npix, d_normal, 3 * npix, d_albedo, 3 * npix); }
 };
 
 // The reprojection (cpt_capi_reproject.cpp; allocated on the frame's first cpt_reproject_accum or
@@ -207,12 +213,33 @@ struct Frame {
     ReprojectState reproject;
     TopupState topup;
     PresentState present;
+
+    // the first-hit aux pair of a CPT_RENDER_AUX render (or cpt_write_aux) of `npix` pixels
+    int ensure_aux(cpt_ctx* c, size_t npix) { return cpt::ctx::ensure_all(c, d_normal, 3 * npix, d_depth, npix); }
 };
 
-// A pair of timing events around a subsystem's last launches, once they have been recorded.
+// A pair of timing events around a subsystem's last launches, once they have been recorded:
+// begin(c, s) before the launches on `s`, end(c, s) behind them.  A call that returns between the
+// two leaves `recorded` as it was; only end, once t1 is recorded, sets it.
 struct TimedSpan {
     DevEvent t0, t1;
     bool recorded = false;
+
+    hipError_t create() {
+        const hipError_t e = t0.create();
+        return e != hipSuccess ? e : t1.create();
+    }
+    int begin(cpt_ctx* c, hipStream_t s) {
+        using cpt::ctx::fail;
+        HIP_TRY(c, hipEventRecord(t0, s));
+        return CPT_OK;
+    }
+    int end(cpt_ctx* c, hipStream_t s) {
+        using cpt::ctx::fail;
+        HIP_TRY(c, hipEventRecord(t1, s));
+        recorded = true;
+        return CPT_OK;
+    }
 };
 
 // ======================================================================================
@@ -348,9 +375,36 @@ int require_full_frame(cpt_ctx* c, const char* who);
 // The milliseconds between a span's two events, behind a cpt_last_*_ms entry: CPT_ERR_INVALID_ARG for
 // a NULL c or ms, CPT_ERR_STATE with `nothing_yet` while nothing was recorded; waits for t1 (cpt_capi.cpp).
 int last_span_ms(cpt_ctx* c, TimedSpan cpt_ctx::*span, float* ms, const char* nothing_yet);
-// Drain the context's stream, then report a device-side error of the work it ran.
+// The two drains of the context's stream in front of a blocking host copy.  drain: the device made
+// current and the stream waited for, the kernels' error word left unread.  sync_checked
+// (cpt_capi.cpp): the same, then a device-side error of the work the stream ran is reported (and
+// cleared).  Which entry uses which is kept as it grew, on record here:
+//   drain         cpt_set_frame, cpt_write_rng, cpt_write_accum, cpt_write_aux, cpt_write_moments,
+//                 cpt_write_gbuffer (every write: it replaces what the work before it made),
+//                 cpt_read_aux, cpt_get_stats and the three cpt_get_*_counters
+//   sync_checked  cpt_synchronize, cpt_render / cpt_render_to_count with CPT_RENDER_SYNC,
+//                 cpt_tile_costs, cpt_read_rng, cpt_read_accum, cpt_read_noise, cpt_read_moments,
+//                 cpt_read_filtered, cpt_read_gbuffer, cpt_trace_rays, cpt_pick, cpt_read_mix,
+//                 cpt_read_display_count, cpt_read_exposure, cpt_read_present, cpt_topup_info,
+//                 cpt_debug_read_nodes, cpt_debug_read_tile_order (the top-up list's length)
+// The remaining waits are a stream synchronisation alone, behind work the entry itself queued
+// (cpt_init_rng, the last cpt_adaptive_step, a display pass with a host frame, cpt_math_batch,
+// cpt_selftest_qdiv, cpt_debug_read_tile_order, the scene uploads of cpt_scene.cpp).
+inline int drain(cpt_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream()));
+    return CPT_OK;
+}
 int check_device_error(cpt_ctx* c);
 int sync_checked(cpt_ctx* c);
+// The walk bits a query or a reprojection may pass, and CPT_ERR_INVALID_ARG from `who` for any other.
+constexpr uint32_t WALK_FLAGS = CPT_TRAVERSAL_ORDERED | CPT_TRAVERSAL_PLAIN_LEAVES;
+inline int walk_flags_only(cpt_ctx* c, const char* who, uint32_t flags) {
+    if (!(flags & ~WALK_FLAGS)) return CPT_OK;
+    return fail(c, CPT_ERR_INVALID_ARG, "%s: flags 0x%x (only CPT_TRAVERSAL_* bits)", who, flags);
+}
+// max_depth within 0..MAX_RECURSION_DEPTH_SET; each caller reports it in its own words.
+inline bool max_depth_ok(int max_depth) { return max_depth >= 0 && max_depth <= (int)cpt::MAX_RECURSION_DEPTH_SET; }
 // A device-to-device copy from one of the context's buffers, ordered against the caller's
 // stream without a host wait (cpt_capi.cpp).
 int copy_ordered(cpt_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t caller);

@@ -1,6 +1,7 @@
 // cpt_devmem.hpp — the C-ABI's error helpers (fail, HIP_TRY) and the move-only owners of what a
-// context holds on the device: DevBuf<T> (a unique_ptr with a capacity), HostPinned<T> (pinned host
-// words a stream writes), DevEvent, DevStream.
+// context holds on the device: DevBuf<T> (a unique_ptr with a capacity; ensure_all for several,
+// read_back / write_in for its blocking host copies), HostPinned<T> (pinned host words a stream
+// writes), DevEvent, DevStream.
 // A default-constructed owner is empty; assigning a fresh one releases what it held.  Host code only.
 #pragma once
 
@@ -71,6 +72,30 @@ private:
     T* p_ = nullptr;
     size_t cap_ = 0;
 };
+
+// Room in several buffers, ensure_all(c, a, count_a, b, count_b, ...): in the written order, and the
+// first failure ends it with that failure's status (the buffers before it keep their room).
+inline int ensure_all(cpt_ctx*) { return CPT_OK; }
+template <typename T, typename... Rest>
+int ensure_all(cpt_ctx* c, DevBuf<T>& buf, size_t count, Rest&&... rest) {
+    if (int rc = buf.ensure(c, count)) return rc;
+    return ensure_all(c, rest...);
+}
+
+// The blocking copies between a host array and `count` elements of a buffer (read_back: from
+// element `first` on): hipMemcpy, which waits for the copy and for nothing queued on the context's
+// stream, so the caller drains first (cpt_context.hpp: drain, sync_checked).  Nothing is issued for
+// a count of 0.
+template <typename T>
+int read_back(cpt_ctx* c, void* host, const DevBuf<T>& buf, size_t count, size_t first = 0) {
+    if (count) HIP_TRY(c, hipMemcpy(host, buf.get() + first, count * sizeof(T), hipMemcpyDeviceToHost));
+    return CPT_OK;
+}
+template <typename T>
+int write_in(cpt_ctx* c, DevBuf<T>& buf, const void* host, size_t count) {
+    if (count) HIP_TRY(c, hipMemcpy(buf.get(), host, count * sizeof(T), hipMemcpyHostToDevice));
+    return CPT_OK;
+}
 
 // A few page-locked host words a stream copies results into: the copy is then truly asynchronous
 // (a read-back into pageable memory makes hipMemcpyAsync wait), and the host reads the words after
