@@ -132,6 +132,13 @@ PROTOTYPES = {
     "cpt_present_host": (_I, [_SZ, _I, _P, _F, _I, _F, _I, _P]),
     "cpt_meter_host": (_I, [_SZ, _I, _P, _F, _I, _F, _P, _P]),
     "cpt_present_srgb_thresholds_host": (_I, [_P]),
+    "cpt_aa_coverage": (_I, [_P, _P, _U32, _I, _F]),
+    "cpt_read_aa_coverage": (_I, [_P, _P, _P, _SZ]),
+    "cpt_present_aa": (_I, [_P, _I, _I, _F, _I, _P]),
+    "cpt_last_aa_ms": (_I, [_P, _P]),
+    "cpt_aa_rays_host": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "cpt_aa_coverage_host": (_I, [_I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "cpt_present_aa_host": (_I, [_I, _I, _I, _I, _P, _P, _F, _I, _F, _I, _P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1
@@ -154,6 +161,8 @@ CPT_TONE_REINHARD = 1
 CPT_TONE_ACES = 2
 CPT_TRANSFER_LINEAR = 0
 CPT_TRANSFER_SRGB = 1
+CPT_AA_EDGE = 1
+CPT_AA_UNMATCHED = 2
 CPT_ERR_INVALID_ARG = 1
 CPT_ERR_STATE = 5
 CPT_ERR_UNSUPPORTED = 6

@@ -838,6 +838,32 @@ bool PathTracer::Present(std::vector<uint8_t>& bgra, int tone, bool srgb, bool f
     return cpt_read_present(ctx, bgra.data(), bgra.size()) == CPT_OK || Fail("cpt_read_present", ctx);
 }
 
+// Antialiased presentation: as the presenting calls above.  ResolveCoverage leaves
+// the context's G-buffer at the current camera, which it records as ReadGBuffer does.
+bool PathTracer::ResolveCoverage(int samples, float normal_cos) {
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("ResolveCoverage", CameraCopy::Query, true, cam, lk) || !RequireSingleDevice("ResolveCoverage", "G-buffers")) return false;
+    cpt_ctx* ctx = tiles_[0].ctx;
+    records_.gbuffer_known = false;
+    if (cpt_aa_coverage(ctx, as_cpt(cam), WalkFlags(), samples, normal_cos) != CPT_OK) return Fail("cpt_aa_coverage", ctx);
+    NoteGBuffer(cam);
+    return true;
+}
+
+bool PathTracer::PresentAntialiased(std::vector<uint8_t>& bgra, int tone, bool srgb, bool filtered, float white) {
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("PresentAntialiased", CameraCopy::Query, true, cam, lk) || !RequireSingleDevice("PresentAntialiased", "accumulators"))
+        return false;
+    cpt_ctx* ctx = tiles_[0].ctx;
+    if (cpt_present_aa(ctx, filtered ? CPT_PRESENT_FILTERED : CPT_PRESENT_ACCUM, tone, white, srgb ? CPT_TRANSFER_SRGB : CPT_TRANSFER_LINEAR,
+                       nullptr) != CPT_OK)
+        return Fail("cpt_present_aa", ctx);
+    bgra.resize((size_t)width_ * height_ * 4);
+    return cpt_read_present(ctx, bgra.data(), bgra.size()) == CPT_OK || Fail("cpt_read_present", ctx);
+}
+
 // Counters summed over the tiles (the render flags do not ask for CPT_RENDER_STATS, so these
 // are the counters of the last counting render; GetStats after cpt-level counting renders).
 bool PathTracer::GetStats(cpt_stats* out) {

@@ -22,14 +22,11 @@ bool meter_args_ok(float key, int permille, float adapt) {
     return cpt::filter::finite(key) && key > 0.f && permille >= 0 && permille <= 1000 && adapt >= 0.f && adapt <= 1.f;
 }
 
-// white: > 0 (NaN is refused; +inf turns Reinhard's curve into x / (1 + x))
-bool present_args_ok(int source, int tone, float white, int transfer) {
-    return prs::source_ok(source) && prs::tone_ok(tone) && prs::transfer_ok(transfer) && white > 0.f;
-}
+}  // namespace
 
 // What every call asks of the context before it writes anything: a frame, no adaptive render
 // pending and, for the filtered source, a filter result.  *src: the source plane.
-int require_source(cpt_ctx* c, const char* who, int source, const float4** src) {
+int cpt::ctx::present_source(cpt_ctx* c, const char* who, int source, const float4** src) {
     CPT_REFUSE_PENDING(c, who);
     const Frame& f = c->frame;
     if (!f.set) return fail(c, CPT_ERR_STATE, "%s: no frame (cpt_set_frame first)", who);
@@ -45,7 +42,7 @@ int require_source(cpt_ctx* c, const char* who, int source, const float4** src) 
 
 // The present state of the frame, allocated and initialised on the stream at the frame's first
 // call: the histogram zero, the exposure 1.
-int ensure_state(cpt_ctx* c) {
+int cpt::ctx::present_state(cpt_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     PresentState& p = c->frame.present;
     if (int rc = p.d_bgra.ensure(c, c->npix() * 4)) return rc;
@@ -58,25 +55,14 @@ int ensure_state(cpt_ctx* c) {
     return CPT_OK;
 }
 
-// The source's four floats of pixel i as the host hooks receive them.
-inline void host_pixel(int source, const float* src, size_t i, float S[4]) {
-    const int n = source == CPT_PRESENT_ACCUM ? 4 : 3;
-    S[0] = src[n * i];
-    S[1] = src[n * i + 1];
-    S[2] = src[n * i + 2];
-    S[3] = n == 4 ? src[n * i + 3] : 0.f;
-}
-
-}  // namespace
-
 extern "C" {
 
 int cpt_set_exposure(cpt_ctx* c, float exposure) {
     if (!c) return CPT_ERR_INVALID_ARG;
     if (!(cpt::filter::finite(exposure) && exposure > 0.f))
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_set_exposure: %g (finite, > 0)", (double)exposure);
-    if (int rc = require_source(c, "cpt_set_exposure", CPT_PRESENT_ACCUM, nullptr)) return rc;
-    if (int rc = ensure_state(c)) return rc;
+    if (int rc = present_source(c, "cpt_set_exposure", CPT_PRESENT_ACCUM, nullptr)) return rc;
+    if (int rc = present_state(c)) return rc;
     HIP_TRY(c, hipMemsetD32Async((hipDeviceptr_t)(c->frame.present.d_words.get() + EXPOSURE_WORD), (int)prs::bits_of(exposure), 1,
                                  c->stream()));
     return CPT_OK;
@@ -88,8 +74,8 @@ int cpt_meter_exposure(cpt_ctx* c, int source, float key, int permille, float ad
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_meter_exposure: source %d, key %g (finite, > 0), permille %d (0..1000), adapt %g (0..1)",
                     source, (double)key, permille, (double)adapt);
     const float4* src = nullptr;
-    if (int rc = require_source(c, "cpt_meter_exposure", source, &src)) return rc;
-    if (int rc = ensure_state(c)) return rc;
+    if (int rc = present_source(c, "cpt_meter_exposure", source, &src)) return rc;
+    if (int rc = present_state(c)) return rc;
     hipStream_t s = c->stream();
     if (int rc = c->t_present.begin(c, s)) return rc;
     HIP_TRY(c, cpt::launch_meter(src, c->npix(), source, key, permille, adapt, c->frame.present.d_words, c->grid.cus, s));
@@ -98,8 +84,8 @@ int cpt_meter_exposure(cpt_ctx* c, int source, float key, int permille, float ad
 
 int cpt_read_exposure(cpt_ctx* c, float* exposure, uint32_t* hist257) {
     if (!c) return CPT_ERR_INVALID_ARG;
-    if (int rc = require_source(c, "cpt_read_exposure", CPT_PRESENT_ACCUM, nullptr)) return rc;
-    if (int rc = ensure_state(c)) return rc;
+    if (int rc = present_source(c, "cpt_read_exposure", CPT_PRESENT_ACCUM, nullptr)) return rc;
+    if (int rc = present_state(c)) return rc;
     if (int rc = sync_checked(c)) return rc;
     uint32_t words[prs::HIST_WORDS + 1];
     if (int rc = read_back(c, words, c->frame.present.d_words, prs::HIST_WORDS + 1)) return rc;
@@ -110,12 +96,12 @@ int cpt_read_exposure(cpt_ctx* c, float* exposure, uint32_t* hist257) {
 
 int cpt_present(cpt_ctx* c, int source, int tone, float white, int transfer, uint8_t* bgra_host) {
     if (!c) return CPT_ERR_INVALID_ARG;
-    if (!present_args_ok(source, tone, white, transfer))
+    if (!prs::args_ok(source, tone, white, transfer))
         return fail(c, CPT_ERR_INVALID_ARG, "cpt_present: source %d, tone %d, white %g (> 0), transfer %d", source, tone, (double)white,
                     transfer);
     const float4* src = nullptr;
-    if (int rc = require_source(c, "cpt_present", source, &src)) return rc;
-    if (int rc = ensure_state(c)) return rc;
+    if (int rc = present_source(c, "cpt_present", source, &src)) return rc;
+    if (int rc = present_state(c)) return rc;
     PresentState& p = c->frame.present;
     hipStream_t s = c->stream();
     const size_t npix = c->npix();
@@ -151,10 +137,10 @@ int cpt_last_present_ms(cpt_ctx* c, float* ms) {
 }
 
 int cpt_present_host(size_t npix, int source, const float* src, float exposure, int tone, float white, int transfer, uint8_t* bgra) {
-    if ((npix && (!src || !bgra)) || !present_args_ok(source, tone, white, transfer)) return CPT_ERR_INVALID_ARG;
+    if ((npix && (!src || !bgra)) || !prs::args_ok(source, tone, white, transfer)) return CPT_ERR_INVALID_ARG;
     for (size_t i = 0; i < npix; ++i) {
         float S[4];
-        host_pixel(source, src, i, S);
+        prs::host_pixel(source, src, i, S);
         const uint32_t w = prs::pixel_word(source, S[0], S[1], S[2], S[3], exposure, tone, white, transfer, SRGB_T);
         bgra[4 * i] = (uint8_t)w;
         bgra[4 * i + 1] = (uint8_t)(w >> 8);
@@ -170,7 +156,7 @@ int cpt_meter_host(size_t npix, int source, const float* src, float key, int per
     uint32_t hist[prs::HIST_WORDS] = {0};
     for (size_t i = 0; i < npix; ++i) {
         float S[4];
-        host_pixel(source, src, i, S);
+        prs::host_pixel(source, src, i, S);
         ++hist[prs::meter_word(source, S[0], S[1], S[2], S[3])];
     }
     *exposure = prs::resolve(hist, *exposure, key, permille, adapt);

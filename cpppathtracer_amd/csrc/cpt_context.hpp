@@ -5,7 +5,8 @@
 // cpt_capi_display.cpp (display path), cpt_capi_query.cpp (G-buffer, ray queries, picking),
 // cpt_capi_reproject.cpp (reprojection to a moved camera), cpt_capi_topup.cpp (top-up render),
 // cpt_capi_probes.cpp (diagnostic probes, self-tests), cpt_capi_present.cpp (presenting, DESIGN.md
-// §26) and cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  What those files
+// §26), cpt_antialias_capi.cpp (antialiased presentation) and cpt_scene.cpp (scene
+// upload, material slots, walk trees, device refit).  What those files
 // would otherwise each spell out is here once: the timed spans (TimedSpan), the buffer lists
 // (GBufferState::ensure, Frame::ensure_aux; ensure_all, read_back and write_in are cpt_devmem.hpp's),
 // the two drains, and the argument checks more than one file makes.  Host code only.
@@ -196,6 +197,15 @@ struct PresentState {
     bool presented = false;     // a cpt_present has been queued since cpt_set_frame
 };
 
+// Antialiased presentation (cpt_antialias_capi.cpp; allocated on the frame's first
+// cpt_aa_coverage).
+struct AntialiasState {
+    DevBuf<uint4> d_cov;        // a 16-byte coverage word per pixel: nine counts, the flags, padding
+    DevBuf<uint32_t> d_list;    // the edge pixels of the last cpt_aa_coverage, in no particular order
+    DevBuf<uint32_t> d_count;   // their number, a device word
+    int samples = 0;            // S of the last cpt_aa_coverage queued since cpt_set_frame (0: none)
+};
+
 struct Frame {
     bool set = false, rng_set = false;
     DevBuf<int32_t> d_rows;
@@ -213,6 +223,7 @@ struct Frame {
     ReprojectState reproject;
     TopupState topup;
     PresentState present;
+    AntialiasState antialias;
 
     // the first-hit aux pair of a CPT_RENDER_AUX render (or cpt_write_aux) of `npix` pixels
     int ensure_aux(cpt_ctx* c, size_t npix) { return cpt::ctx::ensure_all(c, d_normal, 3 * npix, d_depth, npix); }
@@ -260,6 +271,7 @@ struct cpt_ctx {
     DevEvent ev_reproject[2];   // ... and the two points between them: after each G-buffer trace
     bool reproject_tracked = false;   // ... of a tracked call: the trace at `from` did not run
     TimedSpan t_present;   // the last cpt_meter_exposure's or cpt_present's launches
+    TimedSpan t_aa;        // the last cpt_aa_coverage's launches behind its G-buffer trace
     std::string err;
 
     // scene
@@ -420,6 +432,13 @@ size_t n_tiles(const cpt_ctx* c);
 int cost_pilot_passes(int spp);
 int cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStream_t s);
 int consolidation_slab(cpt_ctx* c, cpt::KParams& p, int spp, uint32_t flags);
+
+// cpt_capi_present.cpp, shared with cpt_antialias_capi.cpp.  present_source: what every presenting
+// call asks of the context before it writes anything (a frame, no adaptive render pending and, for
+// the filtered source, a filter result); *src: the source plane.  present_state: the frame's
+// present state, allocated and initialised on the stream at its first call (histogram 0, exposure 1).
+int present_source(cpt_ctx* c, const char* who, int source, const float4** src);
+int present_state(cpt_ctx* c);
 
 // cpt_scene.cpp
 int material_slot(cpt_ctx* c, const cpt_material& m);

@@ -142,6 +142,20 @@ inline float resolve(const uint32_t* hist, float e, float key, int permille, flo
 __host__ __device__ inline bool source_ok(int s) { return s == CPT_PRESENT_ACCUM || s == CPT_PRESENT_FILTERED; }
 __host__ __device__ inline bool tone_ok(int t) { return t == CPT_TONE_CLAMP || t == CPT_TONE_REINHARD || t == CPT_TONE_ACES; }
 __host__ __device__ inline bool transfer_ok(int t) { return t == CPT_TRANSFER_LINEAR || t == CPT_TRANSFER_SRGB; }
+// cpt_present's arguments; white: > 0 (NaN is refused; +inf turns Reinhard's curve into x / (1 + x))
+__host__ __device__ inline bool args_ok(int source, int tone, float white, int transfer) {
+    return source_ok(source) && tone_ok(tone) && transfer_ok(transfer) && white > 0.f;
+}
+
+// The source's four floats of pixel i as the host hooks receive them: [npix][4] for the
+// accumulator, [npix][3] for the filtered rgb.
+inline void host_pixel(int source, const float* src, size_t i, float S[4]) {
+    const int n = source == CPT_PRESENT_ACCUM ? 4 : 3;
+    S[0] = src[n * i];
+    S[1] = src[n * i + 1];
+    S[2] = src[n * i + 2];
+    S[3] = n == 4 ? src[n * i + 3] : 0.f;
+}
 
 }  // namespace present
 }  // namespace cpt

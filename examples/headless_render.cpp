@@ -7,14 +7,16 @@
 //                [--objects N] [--animate K [--animate-step X]] [--pick X,Y] [--orbit N [--reproject]]
 //                [--orbit N [--animate K] --display-reproject on|off|edits --bgra frame.bin]
 //                [--animate K --reproject] [--fill T] [--filter-spatial [LEVELS] [--look-aside]]
-//                [--present clamp|reinhard|aces [--exposure auto|X] [--linear] --bgra frame.bin]
+//                [--present clamp|reinhard|aces [--exposure auto|X] [--linear] [--aa 2|4] --bgra frame.bin]
 //
 // --present CURVE (with plain --spp, and with --orbit N --reproject [--fill T] [--filter-spatial]; not
 // with --display-reproject or --dispatch, whose loop has its own 8-bit output): the last frame, the
 // filtered one with --filter-spatial, is presented through the exposure, the tone curve and the sRGB
 // transfer (PathTracer::Present; --linear: the reference's 255.99 * linear bytes) and
 // --bgra gets the BGRA8 frame.  --exposure auto meters the frame first (PathTracer::MeterExposure: the
-// median luminance to 0.18), --exposure X sets it; without either it is 1.
+// median luminance to 0.18), --exposure X sets it; without either it is 1.  --aa S (2 or 4; only with
+// --present): S x S first-hit rays inside every edge pixel and the coverage-weighted presentation
+// (PathTracer::ResolveCoverage, PresentAntialiased).
 //
 // --filter-spatial [LEVELS] (without --adaptive: with plain --spp, and with --orbit N --reproject
 // [--fill T]): the last frame is filtered without moments, its variance estimated from each pixel's
@@ -206,6 +208,7 @@ int main(int argc, char** argv) {
     std::string display_reproject;   // "", "on" or "off"
     std::string present, exposure;   // --present clamp|reinhard|aces, --exposure auto|X
     bool present_linear = false;     // --linear: CPT_TRANSFER_LINEAR
+    int aa = 0;                      // --aa 2|4: antialiased presentation
     for (int i = 1; i < argc; i += 2) {
         std::string k = argv[i];
         if (k == "--filter") {
@@ -259,6 +262,7 @@ int main(int argc, char** argv) {
         else if (k == "--display-reproject") display_reproject = v;
         else if (k == "--present") present = v;
         else if (k == "--exposure") exposure = v;
+        else if (k == "--aa") aa = std::stoi(v);
         else if (k == "--adaptive") adaptive = std::stof(v);
         else if (k == "--min-spp") min_spp = std::stoi(v);
         else if (k == "--batch") batch = std::stoi(v);
@@ -349,6 +353,10 @@ int main(int argc, char** argv) {
                             "--orbit N --reproject [--fill T] [--filter-spatial]; not --display-reproject, --dispatch, --adaptive or --animate\n");
             return 2;
         }
+    }
+    if (aa != 0 && (present_tone < 0 || (aa != 2 && aa != 4))) {
+        fprintf(stderr, "--aa wants 2 or 4, and --present\n");
+        return 2;
     }
     if (!display_reproject.empty()) {
         if (orbit <= 0 || (display_reproject != "on" && display_reproject != "off" && display_reproject != "edits")) {
@@ -506,7 +514,10 @@ int main(int argc, char** argv) {
         if (exposure == "auto" && !tracer.MeterExposure(from_filtered)) { fprintf(stderr, "MeterExposure: %s\n", tracer.LastError().c_str()); return 1; }
         if (present_exposure > 0.f && !tracer.SetExposure(present_exposure)) { fprintf(stderr, "SetExposure: %s\n", tracer.LastError().c_str()); return 1; }
         std::vector<uint8_t> frame;
-        if (!tracer.Present(frame, present_tone, !present_linear, from_filtered)) { fprintf(stderr, "Present: %s\n", tracer.LastError().c_str()); return 1; }
+        if (aa != 0) {
+            if (!tracer.ResolveCoverage(aa)) { fprintf(stderr, "ResolveCoverage: %s\n", tracer.LastError().c_str()); return 1; }
+            if (!tracer.PresentAntialiased(frame, present_tone, !present_linear, from_filtered)) { fprintf(stderr, "PresentAntialiased: %s\n", tracer.LastError().c_str()); return 1; }
+        } else if (!tracer.Present(frame, present_tone, !present_linear, from_filtered)) { fprintf(stderr, "Present: %s\n", tracer.LastError().c_str()); return 1; }
         std::ofstream f(bgra_out, std::ios::binary);
         f.write(reinterpret_cast<const char*>(frame.data()), (std::streamsize)frame.size());
         printf("presented: %s, %s, exposure %s\n", present.c_str(), present_linear ? "linear" : "sRGB", exposure.empty() ? "1" : exposure.c_str());

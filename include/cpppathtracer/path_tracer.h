@@ -13,7 +13,7 @@
 //   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance, FilterRadianceSpatial,
 //   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
 //   Reproject, CaptureHistory, ReprojectTracked, RenderToCount, SetDisplayReprojection, SetExposure,
-//   MeterExposure, Present, GetStats, Stop.
+//   MeterExposure, Present, ResolveCoverage, PresentAntialiased, GetStats, Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -178,6 +178,17 @@ public:
     bool SetExposure(float exposure);
     bool MeterExposure(bool filtered = false, float key = 0.18f, int permille = 500, float adapt = 1.0f);
     bool Present(std::vector<uint8_t>& bgra, int tone = CPT_TONE_ACES, bool srgb = true, bool filtered = false, float white = 4.0f);
+    // Antialiased presentation (cpt_aa_coverage, cpt_present_aa; an addition: RayGen
+    // shoots every pass of a pixel through the same point of it).  ResolveCoverage traces samples x
+    // samples (2 or 4) first-hit rays inside every pixel on a geometric edge at the current camera
+    // (an id change among its 8 neighbours, or a normal turned past normal_cos) and attributes them
+    // to the neighbours whose centre saw the same surface; it leaves the G-buffer at that camera.
+    // PresentAntialiased is Present with every pixel the coverage-weighted mix of those neighbours'
+    // tone-mapped colours; it needs a ResolveCoverage since the frame was made, and a new one after
+    // a camera move or an object edit.  Not available with SetDevices(n > 1) (false, LastError).
+    bool ResolveCoverage(int samples = 4, float normal_cos = 0.9f);
+    bool PresentAntialiased(std::vector<uint8_t>& bgra, int tone = CPT_TONE_ACES, bool srgb = true, bool filtered = false,
+                            float white = 4.0f);
     bool GetStats(cpt_stats* out);
     void Stop();                                 // stop the render thread (also in ~PathTracer)
     const std::string& LastError() const { return err_; }

@@ -862,6 +862,69 @@ int cpt_meter_host(size_t npix, int source, const float* src, float key, int per
                    uint32_t* hist257);
 int cpt_present_srgb_thresholds_host(float* t256);
 
+/* Antialiased presentation (an addition; CPT_ABI_VERSION stays 1).  Every pass of a
+ * pixel goes through the same point of it (RayGen has no pixel offset), so a frame converges to a
+ * point-sampled image with stair-stepped silhouettes.  Shading is expensive and visibility cheap:
+ * cpt_aa_coverage traces S x S first-hit rays inside each pixel on a geometric edge and attributes
+ * every sub-sample to the pixel of the 3x3 block whose centre ray saw the same surface;
+ * cpt_present_aa presents the coverage-weighted mix of those pixels' tone-mapped colours (after
+ * Chajdas, McGuire, Luebke 2011).  The integrator, the accumulator and cpt_present are untouched.
+ * All of it is f32 + - * /, RayGen's sqrt, comparisons and integers (cpt_antialias.hpp), so the
+ * device, the host hooks below and a numpy restatement agree bit for bit.
+ *   Sub-sample s = j S + i (0 <= i, j < S; S = 2 or 4) of pixel (x, y): RayGen's ray at zero lens
+ *     offset through ((x + ox) / W, (y + oy) / H), ox = (2i + 1 - S) / 2S and oy alike (negative
+ *     quotients at x = 0 or y = 0 are kept), tmin 0, tmax 1e30, walked as cpt_gbuffer walks under
+ *     the same CPT_TRAVERSAL_* flags.
+ *   Edge pixel p: some in-frame 8-neighbour q has id_q != id_p, or id_p >= 0 and
+ *     (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z < normal_cos.  Other pixels trace nothing.
+ *   Attribution: the block's pixels are k = 0..8 row-major, k = 4 is p.  A sub-sample that hit
+ *     (id_s, n_s) matches an in-frame q of the block if id_q == id_s and (id_s == -1 or the dot
+ *     product of n_s and n_q, formed as above, >= normal_cos); the nearest match wins, in integer
+ *     units of 1/2S between (2i + 1 - S, 2j + 1 - S) and (2S dx, 2S dy), ties to k = 4, then to the
+ *     lowest k; with no match it counts on k = 4 and the pixel is flagged unmatched.
+ *   Coverage of p: nine counts c[0..8] summing to S x S (all on k = 4 for a non-edge pixel) and
+ *     the flags CPT_AA_EDGE, CPT_AA_UNMATCHED.
+ *   Resolve: per channel acc = 0, then for k ascending with c[k] > 0: acc = acc + float(c[k]) y_k,
+ *     y_k cpt_present's value of that pixel after source, exposure and tone curve; out = acc / S^2
+ *     (exact); the byte transfer is cpt_present's.  A pixel whose coverage is all on itself gets
+ *     cpt_present's bytes exactly. */
+#define CPT_AA_EDGE      1
+#define CPT_AA_UNMATCHED 2
+/* The coverage of the frame at `cam`, asynchronously on the context's stream.  First makes the
+ * frame's G-buffer at `cam` exactly as cpt_gbuffer(ctx, cam, flags) does (a side effect: the
+ * G-buffer and cpt_last_query_ms are that call's); nothing else of the frame is written.  Needs a
+ * scene and a frame that holds every row 0..height-1 in order (CPT_ERR_STATE otherwise, and while
+ * an adaptive render is pending); samples 2 or 4, normal_cos in [-1, 1], flags within
+ * CPT_TRAVERSAL_*, a camera of the frame's size (CPT_ERR_INVALID_ARG otherwise).  A call refused
+ * for its arguments, for the context's state or for a failed allocation writes nothing.  A HIP
+ * failure behind the G-buffer's trace (an event, a launch: CPT_ERR_HIP) leaves the G-buffer at `cam`
+ * and the coverage, if there was one, as the last successful call left it: run the call again
+ * before cpt_present_aa.  The state is allocated at the frame's first call and dropped by cpt_set_frame;
+ * re-run the call after a camera move or an object edit, as cpt_gbuffer. */
+int cpt_aa_coverage(cpt_ctx* ctx, const cpt_camera* cam, uint32_t flags, int samples, float normal_cos);
+/* The last cpt_aa_coverage's result: counts9 [npix][9] and flags [npix] (either may be NULL);
+ * waits for the stream.  CPT_ERR_STATE before the frame's first cpt_aa_coverage. */
+int cpt_read_aa_coverage(cpt_ctx* ctx, uint8_t* counts9, uint8_t* flags, size_t capacity_pixels);
+/* cpt_present through the coverage: its arguments and errors, and CPT_ERR_STATE with no
+ * cpt_aa_coverage since cpt_set_frame.  Writes cpt_present's plane, so cpt_read_present and
+ * cpt_copy_present_device serve it, and cpt_last_present_ms times it. */
+int cpt_present_aa(cpt_ctx* ctx, int source, int tone, float white, int transfer, uint8_t* bgra_host);
+/* Device time of the last cpt_aa_coverage's edge and coverage kernels (its G-buffer trace is
+ * cpt_last_query_ms's); waits for it. */
+int cpt_last_aa_ms(cpt_ctx* ctx, float* ms);
+/* HOST ONLY, no GPU: the functions the kernels run.  cpt_aa_rays_host: the samples^2 rays of pixel
+ * (x, y) of a W x H image, origin3 / dir3 [samples^2][3] in sub-sample order.
+ * cpt_aa_coverage_host: counts9 [npix][9] and flags [npix] from the G-buffer's id and normal3 planes
+ * and every pixel's sub-sample hits sub_id [npix][samples^2], sub_normal3 [npix][samples^2][3] (-1
+ * and any normal on a miss; read for edge pixels only).  cpt_present_aa_host: bgra [npix][4] from
+ * `src` as cpt_present_host takes it and counts9 (a count on a pixel outside the frame:
+ * CPT_ERR_INVALID_ARG).  Arguments as the device calls'; CPT_ERR_INVALID_ARG likewise. */
+int cpt_aa_rays_host(const cpt_camera* cam, int W, int H, int samples, int x, int y, float* origin3, float* dir3);
+int cpt_aa_coverage_host(int W, int H, int samples, float normal_cos, const int32_t* id, const float* normal3, const int32_t* sub_id,
+                         const float* sub_normal3, uint8_t* counts9, uint8_t* flags);
+int cpt_present_aa_host(int W, int H, int samples, int source, const float* src, const uint8_t* counts9, float exposure, int tone,
+                        float white, int transfer, uint8_t* bgra);
+
 /* HBM streaming-read ceiling of the device (the roofline peak, measured on
  * the box): `iters` grid-stride 16-B-per-lane read passes over a fresh `bytes`-byte buffer
  * (use >> 256 MiB so the Infinity Cache cannot serve it), GB/s from HIP events. */
@@ -920,8 +983,9 @@ int cpt_set_debug_consolidation(cpt_ctx* ctx, uint32_t flags, int keeper_spin_lo
  * that frames small enough for the scalar oracle make every lane take several pixels in turn.
  * max_workgroups > 0: the render's launch and the cost pilot's (cpt_render with
  * CPT_SCHEDULE_COST, cpt_tile_costs) have at most that many workgroups (1024 lanes each with the
- * 4-wide walk's LDS image, 256 without).  lanes_per_wave > 0: only the first lanes_per_wave lanes
- * of each wave take pixels and handed-over chains; the others stay idle.  Every kernel
+ * 4-wide walk's LDS image, 256 without), and so has cpt_aa_coverage's persistent kernel.
+ * lanes_per_wave > 0: only the first lanes_per_wave lanes of each wave take pixels and handed-over
+ * chains; the others stay idle (cpt_aa_coverage's kernel ignores this part).  Every kernel
  * instantiation is well defined for 1 <= lanes_per_wave < 64: the thresholds of the wide walk's
  * leaf rounds and of the deferred sky fetches are shares of the lanes at work, a walk is
  * suspended only after 40 lanes of its wave have finished theirs (never, below 41 lanes), the
