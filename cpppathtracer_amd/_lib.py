@@ -139,6 +139,12 @@ PROTOTYPES = {
     "cpt_aa_rays_host": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "cpt_aa_coverage_host": (_I, [_I, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "cpt_present_aa_host": (_I, [_I, _I, _I, _I, _P, _P, _F, _I, _F, _I, _P]),
+    "cpt_bloom": (_I, [_P, _I, _F, _I]),
+    "cpt_present_bloom": (_I, [_P, _I, _I, _F, _I, _F, _P]),
+    "cpt_read_bloom": (_I, [_P, _I, _P, _SZ]),
+    "cpt_last_bloom_ms": (_I, [_P, _P]),
+    "cpt_bloom_host": (_I, [_I, _I, _I, _P, _F, _F, _I, _I, _P]),
+    "cpt_present_bloom_host": (_I, [_I, _I, _I, _P, _F, _F, _I, _F, _I, _F, _I, _P]),
 }
 
 CPT_RENDER_ACCUMULATE = 0x1
@@ -163,6 +169,7 @@ CPT_TRANSFER_LINEAR = 0
 CPT_TRANSFER_SRGB = 1
 CPT_AA_EDGE = 1
 CPT_AA_UNMATCHED = 2
+CPT_BLOOM_MAX_LEVELS = 8
 CPT_ERR_INVALID_ARG = 1
 CPT_ERR_STATE = 5
 CPT_ERR_UNSUPPORTED = 6

@@ -26,6 +26,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_topup.hip"),
     os.path.join(CSRC, "cpt_present.hip"),
     os.path.join(CSRC, "cpt_antialias.hip"),
+    os.path.join(CSRC, "cpt_bloom.hip"),
     os.path.join(CSRC, "cpt_capi.cpp"),
     os.path.join(CSRC, "cpt_capi_render.cpp"),
     os.path.join(CSRC, "cpt_capi_gather.cpp"),
@@ -38,6 +39,7 @@ SOURCES = [
     os.path.join(CSRC, "cpt_capi_topup.cpp"),
     os.path.join(CSRC, "cpt_capi_present.cpp"),
     os.path.join(CSRC, "cpt_antialias_capi.cpp"),
+    os.path.join(CSRC, "cpt_bloom_capi.cpp"),
     os.path.join(CSRC, "cpt_scene.cpp"),
     os.path.join(CSRC, "cpt_host_bvh.cpp"),
     os.path.join(CSRC, "cpt_host_rng.cpp"),

@@ -864,6 +864,27 @@ bool PathTracer::PresentAntialiased(std::vector<uint8_t>& bgra, int tone, bool s
     return cpt_read_present(ctx, bgra.data(), bgra.size()) == CPT_OK || Fail("cpt_read_present", ctx);
 }
 
+// Bloom: as the presenting calls above.
+bool PathTracer::BuildBloom(bool filtered, float threshold, int levels) {
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("BuildBloom", CameraCopy::Query, true, cam, lk) || !RequireSingleDevice("BuildBloom", "accumulators")) return false;
+    cpt_ctx* ctx = tiles_[0].ctx;
+    return cpt_bloom(ctx, filtered ? CPT_PRESENT_FILTERED : CPT_PRESENT_ACCUM, threshold, levels) == CPT_OK || Fail("cpt_bloom", ctx);
+}
+
+bool PathTracer::PresentBloom(std::vector<uint8_t>& bgra, int tone, bool srgb, bool filtered, float white, float intensity) {
+    MotionalCamera cam;
+    std::unique_lock<std::mutex> lk;
+    if (!Begin("PresentBloom", CameraCopy::Query, true, cam, lk) || !RequireSingleDevice("PresentBloom", "accumulators")) return false;
+    cpt_ctx* ctx = tiles_[0].ctx;
+    if (cpt_present_bloom(ctx, filtered ? CPT_PRESENT_FILTERED : CPT_PRESENT_ACCUM, tone, white, srgb ? CPT_TRANSFER_SRGB : CPT_TRANSFER_LINEAR,
+                          intensity, nullptr) != CPT_OK)
+        return Fail("cpt_present_bloom", ctx);
+    bgra.resize((size_t)width_ * height_ * 4);
+    return cpt_read_present(ctx, bgra.data(), bgra.size()) == CPT_OK || Fail("cpt_read_present", ctx);
+}
+
 // Counters summed over the tiles (the render flags do not ask for CPT_RENDER_STATS, so these
 // are the counters of the last counting render; GetStats after cpt-level counting renders).
 bool PathTracer::GetStats(cpt_stats* out) {

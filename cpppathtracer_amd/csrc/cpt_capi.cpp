@@ -153,7 +153,7 @@ int cpt_create(int device, cpt_ctx** out) {
     if (e == hipSuccess) e = hipDeviceGetAttribute(&c->grid.cus, hipDeviceAttributeMultiprocessorCount, device);
     c->grid.cus = std::max(c->grid.cus, 1);
     if (e == hipSuccess) e = c->own_stream.create(hipStreamNonBlocking);
-    for (TimedSpan* t : {&c->t_render, &c->t_display, &c->t_filter, &c->t_query, &c->t_reproject, &c->t_present, &c->t_aa})
+    for (TimedSpan* t : {&c->t_render, &c->t_display, &c->t_filter, &c->t_query, &c->t_reproject, &c->t_present, &c->t_aa, &c->t_bloom})
         if (e == hipSuccess) e = t->create();
     for (DevEvent* ev : {&c->ev_main, &c->ev_reproject[0], &c->ev_reproject[1]})   // the points inside two of the spans
         if (e == hipSuccess) e = ev->create();

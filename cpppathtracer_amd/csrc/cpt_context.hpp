@@ -5,8 +5,8 @@
 // cpt_capi_display.cpp (display path), cpt_capi_query.cpp (G-buffer, ray queries, picking),
 // cpt_capi_reproject.cpp (reprojection to a moved camera), cpt_capi_topup.cpp (top-up render),
 // cpt_capi_probes.cpp (diagnostic probes, self-tests), cpt_capi_present.cpp (presenting, DESIGN.md
-// §26), cpt_antialias_capi.cpp (antialiased presentation) and cpt_scene.cpp (scene
-// upload, material slots, walk trees, device refit).  What those files
+// §26), cpt_antialias_capi.cpp (antialiased presentation), cpt_bloom_capi.cpp (bloom,
+// DESIGN.md §28) and cpt_scene.cpp (scene upload, material slots, walk trees, device refit).  What those files
 // would otherwise each spell out is here once: the timed spans (TimedSpan), the buffer lists
 // (GBufferState::ensure, Frame::ensure_aux; ensure_all, read_back and write_in are cpt_devmem.hpp's),
 // the two drains, and the argument checks more than one file makes.  Host code only.
@@ -206,6 +206,12 @@ struct AntialiasState {
     int samples = 0;            // S of the last cpt_aa_coverage queued since cpt_set_frame (0: none)
 };
 
+// Bloom (cpt_bloom_capi.cpp; allocated on the frame's first cpt_bloom).
+struct BloomState {
+    DevBuf<float4> d_pyramid;   // levels 1..CPT_BLOOM_MAX_LEVELS one behind the other (cpt_bloom.hpp Pyramid), rgb + 0 per texel
+    int levels = 0;             // L of the last cpt_bloom queued since cpt_set_frame (0: none)
+};
+
 struct Frame {
     bool set = false, rng_set = false;
     DevBuf<int32_t> d_rows;
@@ -224,6 +230,7 @@ struct Frame {
     TopupState topup;
     PresentState present;
     AntialiasState antialias;
+    BloomState bloom;
 
     // the first-hit aux pair of a CPT_RENDER_AUX render (or cpt_write_aux) of `npix` pixels
     int ensure_aux(cpt_ctx* c, size_t npix) { return cpt::ctx::ensure_all(c, d_normal, 3 * npix, d_depth, npix); }
@@ -272,6 +279,7 @@ struct cpt_ctx {
     bool reproject_tracked = false;   // ... of a tracked call: the trace at `from` did not run
     TimedSpan t_present;   // the last cpt_meter_exposure's or cpt_present's launches
     TimedSpan t_aa;        // the last cpt_aa_coverage's launches behind its G-buffer trace
+    TimedSpan t_bloom;     // the last cpt_bloom's launches
     std::string err;
 
     // scene
@@ -433,7 +441,7 @@ int cost_pilot_passes(int spp);
 int cost_pilot(cpt_ctx* c, const cpt::KParams& p, int passes, hipStream_t s);
 int consolidation_slab(cpt_ctx* c, cpt::KParams& p, int spp, uint32_t flags);
 
-// cpt_capi_present.cpp, shared with cpt_antialias_capi.cpp.  present_source: what every presenting
+// cpt_capi_present.cpp, shared with cpt_antialias_capi.cpp and cpt_bloom_capi.cpp.  present_source: what every presenting
 // call asks of the context before it writes anything (a frame, no adaptive render pending and, for
 // the filtered source, a filter result); *src: the source plane.  present_state: the frame's
 // present state, allocated and initialised on the stream at its first call (histogram 0, exposure 1).

@@ -8,6 +8,7 @@
 //                [--orbit N [--animate K] --display-reproject on|off|edits --bgra frame.bin]
 //                [--animate K --reproject] [--fill T] [--filter-spatial [LEVELS] [--look-aside]]
 //                [--present clamp|reinhard|aces [--exposure auto|X] [--linear] [--aa 2|4] --bgra frame.bin]
+//                [--present CURVE --bloom THRESHOLD[,LEVELS[,INTENSITY]] --bgra frame.bin]
 //
 // --present CURVE (with plain --spp, and with --orbit N --reproject [--fill T] [--filter-spatial]; not
 // with --display-reproject or --dispatch, whose loop has its own 8-bit output): the last frame, the
@@ -16,7 +17,10 @@
 // --bgra gets the BGRA8 frame.  --exposure auto meters the frame first (PathTracer::MeterExposure: the
 // median luminance to 0.18), --exposure X sets it; without either it is 1.  --aa S (2 or 4; only with
 // --present): S x S first-hit rays inside every edge pixel and the coverage-weighted presentation
-// (PathTracer::ResolveCoverage, PresentAntialiased).
+// (PathTracer::ResolveCoverage, PresentAntialiased).  --bloom THRESHOLD[,LEVELS[,INTENSITY]]
+// (only with --present, not with --aa; 6 levels and intensity 0.25 by default): the exposed light
+// above THRESHOLD spread over LEVELS halvings and added in front of the tone curve
+// (PathTracer::BuildBloom, PresentBloom).
 //
 // --filter-spatial [LEVELS] (without --adaptive: with plain --spp, and with --orbit N --reproject
 // [--fill T]): the last frame is filtered without moments, its variance estimated from each pixel's
@@ -209,6 +213,7 @@ int main(int argc, char** argv) {
     std::string present, exposure;   // --present clamp|reinhard|aces, --exposure auto|X
     bool present_linear = false;     // --linear: CPT_TRANSFER_LINEAR
     int aa = 0;                      // --aa 2|4: antialiased presentation
+    std::string bloom;               // --bloom THRESHOLD[,LEVELS[,INTENSITY]]
     for (int i = 1; i < argc; i += 2) {
         std::string k = argv[i];
         if (k == "--filter") {
@@ -263,6 +268,7 @@ int main(int argc, char** argv) {
         else if (k == "--present") present = v;
         else if (k == "--exposure") exposure = v;
         else if (k == "--aa") aa = std::stoi(v);
+        else if (k == "--bloom") bloom = v;
         else if (k == "--adaptive") adaptive = std::stof(v);
         else if (k == "--min-spp") min_spp = std::stoi(v);
         else if (k == "--batch") batch = std::stoi(v);
@@ -357,6 +363,18 @@ int main(int argc, char** argv) {
     if (aa != 0 && (present_tone < 0 || (aa != 2 && aa != 4))) {
         fprintf(stderr, "--aa wants 2 or 4, and --present\n");
         return 2;
+    }
+    float bloom_threshold = 0.f, bloom_intensity = 0.25f;
+    int bloom_levels = 6;
+    if (!bloom.empty()) {
+        char end = 0;
+        const int got = sscanf(bloom.c_str(), "%f,%d,%f%c", &bloom_threshold, &bloom_levels, &bloom_intensity, &end);
+        if (present_tone < 0 || aa != 0 || got < 1 || got > 3 || !(bloom_threshold >= 0.f) || bloom_levels < 1 ||
+            bloom_levels > CPT_BLOOM_MAX_LEVELS || !(bloom_intensity >= 0.f)) {
+            fprintf(stderr, "--bloom wants THRESHOLD[,LEVELS[,INTENSITY]] (>= 0, 1..%d, >= 0) and --present, without --aa\n",
+                    CPT_BLOOM_MAX_LEVELS);
+            return 2;
+        }
     }
     if (!display_reproject.empty()) {
         if (orbit <= 0 || (display_reproject != "on" && display_reproject != "off" && display_reproject != "edits")) {
@@ -517,6 +535,9 @@ int main(int argc, char** argv) {
         if (aa != 0) {
             if (!tracer.ResolveCoverage(aa)) { fprintf(stderr, "ResolveCoverage: %s\n", tracer.LastError().c_str()); return 1; }
             if (!tracer.PresentAntialiased(frame, present_tone, !present_linear, from_filtered)) { fprintf(stderr, "PresentAntialiased: %s\n", tracer.LastError().c_str()); return 1; }
+        } else if (!bloom.empty()) {
+            if (!tracer.BuildBloom(from_filtered, bloom_threshold, bloom_levels)) { fprintf(stderr, "BuildBloom: %s\n", tracer.LastError().c_str()); return 1; }
+            if (!tracer.PresentBloom(frame, present_tone, !present_linear, from_filtered, 4.0f, bloom_intensity)) { fprintf(stderr, "PresentBloom: %s\n", tracer.LastError().c_str()); return 1; }
         } else if (!tracer.Present(frame, present_tone, !present_linear, from_filtered)) { fprintf(stderr, "Present: %s\n", tracer.LastError().c_str()); return 1; }
         std::ofstream f(bgra_out, std::ios::binary);
         f.write(reinterpret_cast<const char*>(frame.data()), (std::streamsize)frame.size());

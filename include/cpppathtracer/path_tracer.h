@@ -13,7 +13,7 @@
 //   SetEnvTexture, Render(spp) (synchronous), RenderAdaptive, ReadNoise, FilterRadiance, FilterRadianceSpatial,
 //   ReadFiltered, SaveFilteredPFM, ReadRadiance, ReadFrameBGRA, SaveRadiancePFM, Pick, ReadGBuffer,
 //   Reproject, CaptureHistory, ReprojectTracked, RenderToCount, SetDisplayReprojection, SetExposure,
-//   MeterExposure, Present, ResolveCoverage, PresentAntialiased, GetStats, Stop.
+//   MeterExposure, Present, ResolveCoverage, PresentAntialiased, BuildBloom, PresentBloom, GetStats, Stop.
 // Errors: the reference logs CUDA errors and continues; here every call that reaches the
 // GPU returns false on failure and LastError() holds the message (no exceptions).
 #pragma once
@@ -189,6 +189,15 @@ public:
     bool ResolveCoverage(int samples = 4, float normal_cos = 0.9f);
     bool PresentAntialiased(std::vector<uint8_t>& bgra, int tone = CPT_TONE_ACES, bool srgb = true, bool filtered = false,
                             float white = 4.0f);
+    // Bloom (cpt_bloom, cpt_present_bloom; an addition).  BuildBloom makes the pyramid
+    // of the light above `threshold` (in exposed units, so after SetExposure / MeterExposure) of the
+    // radiance accumulator, or with `filtered` of the last filter result, over `levels` (1..8) halvings.
+    // PresentBloom is Present with `intensity` (finite, >= 0) times the pyramid's sum added to every
+    // pixel in front of the tone curve; it needs a BuildBloom since the frame was made.  Not available
+    // with SetDevices(n > 1) (false, LastError).
+    bool BuildBloom(bool filtered = false, float threshold = 1.0f, int levels = 6);
+    bool PresentBloom(std::vector<uint8_t>& bgra, int tone = CPT_TONE_ACES, bool srgb = true, bool filtered = false, float white = 4.0f,
+                      float intensity = 0.25f);
     bool GetStats(cpt_stats* out);
     void Stop();                                 // stop the render thread (also in ~PathTracer)
     const std::string& LastError() const { return err_; }

@@ -925,6 +925,60 @@ int cpt_aa_coverage_host(int W, int H, int samples, float normal_cos, const int3
 int cpt_present_aa_host(int W, int H, int samples, int source, const float* src, const uint8_t* counts9, float exposure, int tone,
                         float white, int transfer, uint8_t* bgra);
 
+/* Bloom for presented frames (an addition; CPT_ABI_VERSION stays 1).  The tone curve
+ * sends every value far above the display's white to the same byte; bloom spreads the light above
+ * a threshold over its neighbourhood in front of the curve, so a highlight's size tells how bright
+ * it is.  cpt_bloom builds a pyramid of the source's bright pass; cpt_present_bloom is cpt_present
+ * with the pyramid's sum added to each pixel before the tone curve.  All of it is f32 + - * /,
+ * comparisons and integers in a stated order (cpt_bloom.hpp), so the device, the host hooks below
+ * and a numpy restatement agree bit for bit.  min, c', x, the tone curves and the bytes are
+ * cpt_present's above; luma(r, g, b) = (0.2126 r + 0.7152 g) + 0.0722 b as the meter's.
+ *   Levels: level 0 is the frame, W x H; level l has w_l = (w_(l-1) + 1) / 2 columns (integer
+ *     division) and h_l rows alike; `levels` L in 1..CPT_BLOOM_MAX_LEVELS is the coarsest.  Any frame
+ *     size is allowed (a 1 x 1 frame has eight 1 x 1 levels).
+ *   Bright pass of a pixel (level 0, never stored): x = min(c' e, 65504) per component, e the
+ *     exposure word; l = luma(x); k = l > 0 ? max(l - threshold, 0) / l : 0; b = x k per component.
+ *   Down-step from level l to l + 1 (l = 0..L-1; level 0 is b), per component: texel (X, Y) reads
+ *     columns 2X-1, 2X, 2X+1, 2X+2 and rows 2Y-1..2Y+2 of level l, each index clamped into 0..w_l-1
+ *     (0..h_l-1); each of the four rows first, r = (t0 + 3 t1) + (3 t2 + t3) over its columns, then
+ *     B = ((r0 + 3 r1) + (3 r2 + r3)) * 0.015625 over the rows.
+ *   Up-step from level l + 1 to texel (x, y) of level l: px = x >> 1, qx = px + 1 for odd x and
+ *     px - 1 for even x, clamped into 0..w_(l+1)-1; py, qy alike; h(row) = 3 T[row][px] + T[row][qx];
+ *     up = (3 h(py) + h(qy)) * 0.0625.
+ *   Accumulation: U_L = B_L;  U_l = B_l + up(U_(l+1)) for l = L-1..1.  The glow of a frame pixel is
+ *     g = up(U_1) at (x, y).
+ *   Composite: x' = x + intensity g per component, y = the tone curve of min(x' * 1, 65504), and
+ *     cpt_present's byte of y.  intensity 0, and a threshold above every luminance, give
+ *     cpt_present's bytes.
+ * The pyramid is in exposed units at the exposure of the build: meter, then bloom, then present. */
+#define CPT_BLOOM_MAX_LEVELS 8
+/* Builds U_1..U_levels of `source` (CPT_PRESENT_*) at the current exposure word, asynchronously on
+ * the context's stream.  Needs a frame that holds every row 0..height-1 in order, no adaptive render
+ * pending and, for CPT_PRESENT_FILTERED, a filter result (CPT_ERR_STATE otherwise).  An unknown
+ * source, levels outside 1..CPT_BLOOM_MAX_LEVELS and a threshold that is negative, NaN or infinite:
+ * CPT_ERR_INVALID_ARG.  Every check and every allocation (the pyramid, about a third of the frame in
+ * float4 texels, and the present state, at the frame's first call) precedes the first write: a
+ * refused call writes nothing.  Writes the pyramid alone.  Dropped by cpt_set_frame. */
+int cpt_bloom(cpt_ctx* ctx, int source, float threshold, int levels);
+/* cpt_present with the last cpt_bloom's glow: cpt_present's arguments and errors, intensity finite
+ * and >= 0 (CPT_ERR_INVALID_ARG otherwise), a full frame as cpt_bloom, and CPT_ERR_STATE with no
+ * cpt_bloom since cpt_set_frame.  `source` is the plane x is taken from; the glow is the pyramid's,
+ * whatever it was built from.  Writes cpt_present's plane, so cpt_read_present and
+ * cpt_copy_present_device serve it, and cpt_last_present_ms times it. */
+int cpt_present_bloom(cpt_ctx* ctx, int source, int tone, float white, int transfer, float intensity, uint8_t* bgra_host);
+/* U_level of the last cpt_bloom as [h_level][w_level][3] floats (level in 1..its levels; capacity
+ * in texels); waits for the stream.  CPT_ERR_STATE before the frame's first cpt_bloom. */
+int cpt_read_bloom(cpt_ctx* ctx, int level, float* rgb, size_t capacity_texels);
+/* Device time of the last cpt_bloom's launches (HIP events); waits for it. */
+int cpt_last_bloom_ms(cpt_ctx* ctx, float* ms);
+/* HOST ONLY, no GPU: the functions the kernels run.  `src` as cpt_present_host takes it, for a
+ * W x H frame.  cpt_bloom_host: U_level of a pyramid of `levels` as [h_level][w_level][3].
+ * cpt_present_bloom_host: bgra [W*H][4], the pyramid built at `exposure` from the same plane.
+ * Arguments as the device calls'; CPT_ERR_INVALID_ARG likewise. */
+int cpt_bloom_host(int W, int H, int source, const float* src, float exposure, float threshold, int levels, int level, float* rgb);
+int cpt_present_bloom_host(int W, int H, int source, const float* src, float exposure, float threshold, int levels, float intensity,
+                           int tone, float white, int transfer, uint8_t* bgra);
+
 /* HBM streaming-read ceiling of the device (the roofline peak, measured on
  * the box): `iters` grid-stride 16-B-per-lane read passes over a fresh `bytes`-byte buffer
  * (use >> 256 MiB so the Infinity Cache cannot serve it), GB/s from HIP events. */

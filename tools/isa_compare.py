@@ -28,7 +28,7 @@ sys.path.insert(0, REPO)
 from cpppathtracer_amd import build as _build   # noqa: E402
 
 UNITS = ["cpt_megakernel", "cpt_wavefront", "cpt_query", "cpt_display", "cpt_schedule", "cpt_reproject", "cpt_adaptive",
-         "cpt_filter", "cpt_topup", "cpt_kernels", "cpt_selftest"]
+         "cpt_filter", "cpt_topup", "cpt_kernels", "cpt_selftest", "cpt_present", "cpt_antialias"]
 FLAGS = [f for f in _build.HIPCC_FLAGS if f != "-shared"] + ["--cuda-device-only", "-S"]
 META = [".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
         ".group_segment_fixed_size"]
